@@ -12,10 +12,17 @@ A "step" is one pass of the hot path over one batch of synthetic 1024x1024 tiles
 Default workload = BASELINE.json configs[2] per GPU (ViT-H + InternLM2-7B-shaped + mask decoder, batch 4, bf16, S = 1081);
 N GPUs process N x 4 images (weak scaling; configs[3] at N = 8).  Weights are random-init (no checkpoints exist offline).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = the MFMA GEMM; achieved = algorithmic FLOPs of every GEMM
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step, and the configuration).
+`--dump-outputs DIR` writes what the last timed step computed (low-res logits, masks) as float32 .npy files into DIR before the line
+is printed; the inputs and weights are seeded, so two builds can be compared output for output.
+
+`--full` adds the figures beside the headline, each measured as before:
+`roofline` (dominant kernel = the MFMA GEMM; achieved = algorithmic FLOPs of every GEMM
 launch / their HIP-event durations, sampled on every 5th timed step on the launch stream: an event pair per GEMM on EVERY step cost 1.5 ms
 of a 78 ms step -- rounds 1 - 4 carried that), `step_ms` (min / median / max of the timed steps' own event spans: box and run variance in the record),
-`graph_ms_per_step` (the step replayed from ONE HIP-graph capture, untimed: eager minus this = the cost of launching kernel by kernel)
+`graph_ms_per_step` (the step replayed from ONE HIP-graph capture, untimed: eager minus this = the cost of launching kernel by kernel),
+`mask_iou_vs_reference` / `mask_iou_vs_fp32` (the masks scored against the full-depth fixture and against this library's fp32 mode)
 and `cpu_baseline` (the oracle restated on torch CPU tensors -- multi-threaded fp32 GEMMs, `kind:
 "port-torch"` -- timed on the host cores on a bounded, depth-reduced sample of the same workload, the numpy oracle's figure beside it; N = 1 only).
 """
@@ -525,9 +532,10 @@ def graph_replay_ms(compute, reps: int = 6):
         return None, f"graph capture failed: {type(e).__name__}: {str(e)[:200]}"
 
 
-def timed_steps(step, warmup: int, steps: int, world: int, device: str, on_timed=None, on_step=None):
+def timed_steps(step, warmup: int, steps: int, world: int, device: str, on_timed=None, on_step=None, step_events: bool = True):
     """W untimed steps, then EXACTLY K steps bracketed by barrier + synchronize on both sides; the last step's exchange is inside the
-    timed region; -> (seconds = MAX over ranks, the last gathered result)."""
+    timed region; -> (seconds = MAX over ranks, the last gathered result).  The last step's own result is kept as `timed_steps.last`;
+    `step_events` puts one HIP event on every step boundary (the per-step spread of `--full`)."""
     gpu = device != "cpu"
 
     def barrier():
@@ -553,16 +561,21 @@ def timed_steps(step, warmup: int, steps: int, world: int, device: str, on_timed
         if on_timed:
             on_timed(True)
         marks = []                      # one HIP event per step boundary (K + 1 events: cheap) -> per-step times, for the spread printed beside the mean
+        events = gpu and step_events
+        last = None
         t0 = time.perf_counter()
         for i in range(steps):
             if on_step:
                 on_step(i)
-            if gpu:
+            if events:
                 ev = torch.cuda.Event(enable_timing=True)
                 ev.record()
                 marks.append(ev)
-            step()
-        if gpu:
+            if i == steps - 1:
+                last = step()           # only the last step's result is held: earlier ones are released as before
+            else:
+                step()
+        if events:
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()
             marks.append(ev)
@@ -572,6 +585,7 @@ def timed_steps(step, warmup: int, steps: int, world: int, device: str, on_timed
         if gc_was:
             gc.enable()
         timed_steps.step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(len(marks) - 1)]
+        timed_steps.last = last
         if on_timed:
             on_timed(False)
     if world > 1:
@@ -580,6 +594,23 @@ def timed_steps(step, warmup: int, steps: int, world: int, device: str, on_timed
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return dt, gathered
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6   # --dump-outputs writes at most this many bytes of array data in all
+
+
+def dump_outputs(path: str, arrays: dict):
+    """`--dump-outputs DIR`: every array as float32 DIR/<name>.npy.  When they hold more than DUMP_BUDGET_BYTES together (N > 1: every rank's
+    images), each is cut to a fixed sample of its elements in proportion to its size: the positions drawn by np.random.default_rng(0) over
+    the flattened array, in ascending order -- the same positions in every run with the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in host.values())
+    for k, v in host.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = v.size * DUMP_BUDGET_BYTES // total
+            v = v.reshape(-1)[np.sort(np.random.default_rng(0).choice(v.size, keep, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
 
 
 def dist_teardown(world: int):
@@ -599,13 +630,18 @@ def main():
     ap.add_argument("--llm", default="7b", choices=list(LLM))
     ap.add_argument("--seq", type=int, default=1081)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-iou", action="store_true", help="skip the fp32 run that gives mask_iou_vs_fp32")
-    ap.add_argument("--no-graph", action="store_true", help="skip the HIP-graph replay diagnostic (graph_ms_per_step): kernel traces then hold warm-up + timed steps only")
+    ap.add_argument("--full", action="store_true", help="also the figures beside the headline: roofline, step_ms, graph_ms_per_step, mask_iou_vs_reference / "
+                                                         "mask_iou_vs_fp32, cpu_baseline (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's low-res logits and masks as float32 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-iou", action="store_true", help="--full without the fp32 run that gives mask_iou_vs_fp32 (and without mask_iou_vs_reference)")
+    ap.add_argument("--no-graph", action="store_true", help="--full without the HIP-graph replay diagnostic (graph_ms_per_step)")
     ap.add_argument("--mode", default="mask", choices=["mask", "decode"], help="mask: the headline images/s path; decode: greedy tokens/s of the caption path")
     ap.add_argument("--stub", action="store_true", help="control-path self-test without a GPU (gloo, a stub step): measures nothing")
     ap.add_argument("--vit-fp8", action="store_true", help="fp8 (e4m3) operands for the ViT's LayerNorm-fed linears (qkv, lin1): BASELINE configs[4] 'fp8 MFMA ViT path'; everything else bf16")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(_spawn_ranks(a.gpus, sys.argv[1:]))
@@ -615,6 +651,9 @@ def main():
         dt, gathered = timed_steps(step, a.warmup, a.steps, world, device)
         if world > 1:
             assert gathered is not None and gathered[0].shape[0] == a.batch * world and gathered[1].shape[0] == a.batch * world
+        if rank == 0 and a.dump_outputs:
+            low, mk = gathered[:2] if world > 1 else timed_steps.last
+            dump_outputs(a.dump_outputs, {"low_res_logits": low, "masks": mk})
         if rank == 0:
             print(json.dumps({"metric": "STUB (bench.py control path self-test; not a measurement)", "value": round(a.batch * world * a.steps / dt, 2),
                               "unit": "stub steps", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
@@ -626,6 +665,8 @@ def main():
     if a.mode == "decode":
         if world != 1:
             raise SystemExit("bench.py --mode decode is a single-GPU measurement")
+        if a.dump_outputs:
+            raise SystemExit("bench.py --dump-outputs writes the mask path's outputs (--mode mask)")
         with torch.no_grad():
             decode_mode(a, device)
         return
@@ -638,59 +679,66 @@ def main():
     if os.environ.get("ULLSAM_GEMM_VARIANT"):  # A/B switch for kernel experiments
         from ullsam_amd import _lib
         _lib.load().ullsam_set_gemm_variant(int(os.environ["ULLSAM_GEMM_VARIANT"]))
-    timer = GemmTimer()
-    full = LLM[a.llm] is not None
-    inputs = make_inputs(a.batch, a.seq, device, full)
+    with_llm = LLM[a.llm] is not None
+    inputs = make_inputs(a.batch, a.seq, device, with_llm)
     step = make_step(mask_path_compute(model, inputs, dtype), a.batch, world)
-    # The roofline's event pairs sit inside the timed region, and they are not free: an event pair around every one of the 269 GEMM launches of EVERY timed step cost
-    # 1.5 ms of a 78 ms step (same box, same process order: 77.98 vs 76.45 ms per step with / without them).  They are therefore recorded on every GEMM_EVENT_EVERY-th timed
-    # step only (steps 0, 5, 10, ...: >= 1000 timed launches at the default 20 steps); ULLSAM_BENCH_NO_GEMM_EVENTS=1 switches them off (A/B of their cost; `roofline` is then empty).
-    ev_on = os.environ.get("ULLSAM_BENCH_NO_GEMM_EVENTS") != "1"
-    dt, gathered = timed_steps(step, a.warmup, a.steps, world, device, on_timed=lambda on: setattr(timer, "on", False),
-                               on_step=lambda i: setattr(timer, "on", ev_on and i % GEMM_EVENT_EVERY == 0))
-    event_steps = len([i for i in range(a.steps) if i % GEMM_EVENT_EVERY == 0]) if ev_on else 0
+    if a.full:
+        timer = GemmTimer()
+        # The roofline's event pairs sit inside the timed region, and they are not free: an event pair around every one of the 269 GEMM launches of EVERY timed step cost
+        # 1.5 ms of a 78 ms step (same box, same process order: 77.98 vs 76.45 ms per step with / without them).  They are therefore recorded on every GEMM_EVENT_EVERY-th timed
+        # step only (steps 0, 5, 10, ...: >= 1000 timed launches at the default 20 steps); ULLSAM_BENCH_NO_GEMM_EVENTS=1 switches them off (A/B of their cost; `roofline` is then empty).
+        ev_on = os.environ.get("ULLSAM_BENCH_NO_GEMM_EVENTS") != "1"
+        dt, gathered = timed_steps(step, a.warmup, a.steps, world, device, on_timed=lambda on: setattr(timer, "on", False),
+                                   on_step=lambda i: setattr(timer, "on", ev_on and i % GEMM_EVENT_EVERY == 0))
+    else:   # a plain run: no GEMM event pairs, no per-step events -- the timed steps are the step and nothing else
+        dt, gathered = timed_steps(step, a.warmup, a.steps, world, device, step_events=False)
     if world > 1:
         assert gathered is not None and gathered[0].shape[0] == a.batch * world and gathered[1].shape[0] == a.batch * world
-    n_launch, gemm_ms, gemm_flops = timer.summary()
-    graph_ms, graph_note = None, None
-    if device != "cpu" and world == 1 and not a.no_graph:   # the same step ONCE MORE as a HIP-graph replay, outside the timed region: launch gaps of the eager loop show as eager - graph
-        graph_ms, graph_note = graph_replay_ms(mask_path_compute(model, inputs, dtype))
-    traffic, traffic_note = (None, "not the default workload")
-    if a.vit == "h" and a.llm == "7b" and a.batch == 4 and a.dtype == "bf16":
-        traffic, traffic_note = traffic_record()
+    if rank == 0 and a.dump_outputs:
+        low, mk = gathered[:2] if world > 1 else timed_steps.last
+        dump_outputs(a.dump_outputs, {"low_res_logits": low, "masks": mk})
     images = a.batch * world * a.steps
     value = images / dt
-    peak = PEAK_BF16_TFLOPS if a.dtype == "bf16" else 157.3
-    ach = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
     line = {
         "metric": "images/s end-to-end (ViT+LLM+mask) 1024^2", "value": round(value, 4), "unit": "images/s", "n_gpus": world,
         "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": a.dtype, "data": DATA_NOTE,
-        "step_ms": step_spread(getattr(timed_steps, "step_ms", [])),
-        "graph_ms_per_step": graph_ms, "graph_note": graph_note,
         "config": {"workload": (f"uLLSAM mask path (app.py:580-645): SAM ViT-{a.vit.upper()} + "
-                                + (f"InternLM2-{a.llm}-shaped prefill S={a.seq} + " if full else "")
+                                + (f"InternLM2-{a.llm}-shaped prefill S={a.seq} + " if with_llm else "")
                                 + f"prompt encoder + mask decoder + x4 upsample/threshold, 1 point prompt/image, batch {a.batch}/GPU"),
-                   "batch_per_gpu": a.batch, "global_batch": a.batch * world, "seq_len": a.seq if full else 0,
+                   "batch_per_gpu": a.batch, "global_batch": a.batch * world, "seq_len": a.seq if with_llm else 0,
                    "vit_linears": "fp8 e4m3 operands for qkv / lin1 (per-row / per-channel scales), proj / lin2 bf16" if a.vit_fp8 else "bf16",
                    "parallelism": f"dp{world} (images sharded, weights replicated, one RCCL all-gather of logits+masks per step, overlapped with the next step)",
                    "ranks": ranks_seen},
-        "roofline": {"bound": "mfma", "kernel": "ullsam_gemm (every nn.Linear / conv-as-GEMM launch)", "achieved": round(ach, 2),
-                     "peak": peak, "unit": "TFLOP/s", "frac": round(ach / peak, 4), "traffic": traffic, "traffic_unit": traffic_note,
-                     "algorithmic_bytes_per_launch": round(timer.alg_bytes / max(n_launch, 1)),
-                     "launches_per_step": n_launch // max(event_steps, 1), "avg_launch_us": round(gemm_ms * 1e3 / max(n_launch, 1), 2),
-                     "event_timed_steps": event_steps, "event_timed_launches": n_launch,
-                     "gemm_share_of_step": round(gemm_ms / max(event_steps, 1) / (dt / a.steps * 1e3), 4)},
     }
-    if rank == 0 and a.dtype == "bf16" and not a.no_iou and a.vit == "h" and a.llm == "7b" and a.seq == 1081:
-        line["mask_iou_vs_reference"] = mask_iou_vs_reference(model, inputs, dtype)
-    if rank == 0 and world == 1 and a.dtype == "bf16" and not a.no_iou:
-        line["mask_iou_vs_fp32"] = mask_iou_vs_fp32(model, a.vit, a.llm, inputs, device)
-    if a.vit_fp8:   # the GEMM timer wraps ops.gemm / gemm_qkv_rope only: the fp8 launches (ops.gemm_fp8) are outside `roofline`
-        line["roofline"]["note"] = "bf16 GEMM launches only; the fp8 qkv / lin1 launches are not in this figure"
-    if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+    if a.full:
+        event_steps = len([i for i in range(a.steps) if i % GEMM_EVENT_EVERY == 0]) if ev_on else 0
+        n_launch, gemm_ms, gemm_flops = timer.summary()
+        graph_ms, graph_note = None, None
+        if device != "cpu" and world == 1 and not a.no_graph:   # the same step ONCE MORE as a HIP-graph replay, outside the timed region: launch gaps of the eager loop show as eager - graph
+            graph_ms, graph_note = graph_replay_ms(mask_path_compute(model, inputs, dtype))
+        traffic, traffic_note = (None, "not the default workload")
+        if a.vit == "h" and a.llm == "7b" and a.batch == 4 and a.dtype == "bf16":
+            traffic, traffic_note = traffic_record()
+        peak = PEAK_BF16_TFLOPS if a.dtype == "bf16" else 157.3
+        ach = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+        line["step_ms"] = step_spread(getattr(timed_steps, "step_ms", []))
+        line["graph_ms_per_step"], line["graph_note"] = graph_ms, graph_note
+        line["roofline"] = {"bound": "mfma", "kernel": "ullsam_gemm (every nn.Linear / conv-as-GEMM launch)", "achieved": round(ach, 2),
+                            "peak": peak, "unit": "TFLOP/s", "frac": round(ach / peak, 4), "traffic": traffic, "traffic_unit": traffic_note,
+                            "algorithmic_bytes_per_launch": round(timer.alg_bytes / max(n_launch, 1)),
+                            "launches_per_step": n_launch // max(event_steps, 1), "avg_launch_us": round(gemm_ms * 1e3 / max(n_launch, 1), 2),
+                            "event_timed_steps": event_steps, "event_timed_launches": n_launch,
+                            "gemm_share_of_step": round(gemm_ms / max(event_steps, 1) / (dt / a.steps * 1e3), 4)}
+        if rank == 0 and a.dtype == "bf16" and not a.no_iou and a.vit == "h" and a.llm == "7b" and a.seq == 1081:
+            line["mask_iou_vs_reference"] = mask_iou_vs_reference(model, inputs, dtype)
+        if rank == 0 and world == 1 and a.dtype == "bf16" and not a.no_iou:
+            line["mask_iou_vs_fp32"] = mask_iou_vs_fp32(model, a.vit, a.llm, inputs, device)
+        if a.vit_fp8:   # the GEMM timer wraps ops.gemm / gemm_qkv_rope only: the fp8 launches (ops.gemm_fp8) are outside `roofline`
+            line["roofline"]["note"] = "bf16 GEMM launches only; the fp8 qkv / lin1 launches are not in this figure"
+        if rank == 0 and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(a.vit, a.llm, a.seq)
+    if rank == 0:
         print(json.dumps(line), flush=True)
     dist_teardown(world)
 

@@ -439,6 +439,33 @@ def test_bench_gpus2_control_path_runs_end_to_end_in_stub_mode():
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stdout + r.stderr)
 
 
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` (stub step, no GPU): DIR/<name>.npy in float32 holding what the last timed step returned; two runs with the same
+    arguments write the same arrays; the line counts exactly the --steps timed steps.  The sampling of outputs over the byte budget keeps fixed positions."""
+    import json
+    import subprocess
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--stub", "--steps", "3", "--warmup", "1", "--batch", "2",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, env=env, cwd=ROOT, timeout=300)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+    low, mk = bench.stub_compute(2, 0)()
+    for name, want in (("low_res_logits", low), ("masks", mk)):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        assert np.array_equal(a, want.float().numpy())
+    big = {"x": torch.arange(bench.DUMP_BUDGET_BYTES // 4 + 1000, dtype=torch.float32), "y": torch.ones(10)}
+    bench.dump_outputs(str(tmp_path / "c"), big)
+    bench.dump_outputs(str(tmp_path / "d"), big)
+    x, x2 = np.load(tmp_path / "c" / "x.npy"), np.load(tmp_path / "d" / "x.npy")
+    assert np.array_equal(x, x2) and (np.diff(x) > 0).all() and x.nbytes + np.load(tmp_path / "c" / "y.npy").nbytes <= bench.DUMP_BUDGET_BYTES
+
+
 def test_bench_init_rule_is_the_fixture_filler_rule():
     """bench.py fills its model by ullsam_amd.utils.synthetic.fixture_param (rule table: param_init_rule); the reference-generated fixtures
     (incl. the full-depth one) were filled by oracle.fill_param.  Same (mean, std) for every parameter of the composite model, so the bench's
