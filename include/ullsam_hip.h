@@ -27,7 +27,7 @@ extern "C" {
 
 /* Bumped whenever an entry point is added or a signature changes.  The Python binding refuses a library that reports another
    version (a stale libullsam_hip.so would otherwise receive shifted arguments, e.g. a row count where the stream is expected). */
-#define ULLSAM_ABI_VERSION 11
+#define ULLSAM_ABI_VERSION 12
 
 const char* ullsam_last_error_string(void);
 int ullsam_abi_version(void); /* == ULLSAM_ABI_VERSION of the header the library was built from */
@@ -145,8 +145,9 @@ int ullsam_train_attn_rows(float* S, float* dP, const float* bias_h, const float
                            int B, int H, int Sq, int Sk, int kw, int causal, int have_p, void* stream);
 /* 0: keep the row pass on its three-pass form (tests compare it with the register-resident form used for Sk <= 4096); returns the previous setting */
 int ullsam_train_set_rows_reg(int on);
-/* InternLM2RMSNorm backward (modeling_internlm2.py:75-89); dw may be NULL (frozen LLM) */
-int ullsam_train_rmsnorm_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, long rows, int D, float eps, void* stream);
+/* InternLM2RMSNorm backward (modeling_internlm2.py:75-89); dw_rows NULL (frozen LLM) or [rows, D]: the rows of dy * xhat, whose column sums
+ * (ullsam_train_colsum: ordered, no atomics) are dw -- a trainable norm weight (train.py's SFT stage) gets the same bits in every run (version 12) */
+int ullsam_train_rmsnorm_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw_rows, long rows, int D, float eps, void* stream);
 /* apply_rotary_pos_emb (modeling_internlm2.py:233-247) on rows [tokens, heads, hd]; adjoint != 0: its transpose (the backward) */
 int ullsam_train_rope(const float* x, const int* pos, const float* cos_tab, const float* sin_tab, float* out, long tokens, int heads, int hd,
                       int tab_rows, int adjoint, void* stream);
@@ -168,6 +169,18 @@ int ullsam_train_seg_loss_bwd(const float* x, const float* t, const float* sums,
 int ullsam_train_cross_entropy(const float* logits, long ld, const long long* labels, float* lse, float* loss_rows, float* out2, long rows, int V, void* stream);
 int ullsam_train_cross_entropy_bwd(const float* logits, long ld, const long long* labels, const float* lse, const float* out2, const float* gscale, float* dlogits,
                                    long ldx, long rows, int V, void* stream);   /* dlogits rows of ldx >= V floats: columns V .. ldx - 1 are zeroed (GEMM padding) */
+/* The same gradient for a TRAINABLE LM head (train.py:284-318, 400-480: the SFT stage leaves language_model.output trainable), in bf16 and in the head GEMMs' own
+ * operand layouts, written in one pass over the logits: dlog [rows, ldd] row-major (dX = dlog W; ldd >= Vp) and dlogT [Vp, ldt] (dW = dlog^T h; ldt >= Rp), Vp / Rp = V /
+ * rows rounded up to 64, the pads zero.  Each value is the round-to-nearest-even bf16 of what ullsam_train_cross_entropy_bwd writes.  dlog or dlogT NULL: that layout is skipped. */
+int ullsam_train_cross_entropy_bwd_bf16(const float* logits, long ld, const long long* labels, const float* lse, const float* out2, const float* gscale,
+                                        void* dlog, long ldd, void* dlogT, long ldt, long rows, int V, void* stream);
+/* The gradient of the token embeddings nn.Embedding(V, D, padding_idx=pad_token_id) (modeling_internlm2.py:808,815; embedding_dense_backward) behind the
+ * <IMG_CONTEXT> splice `input_embeds[selected] * 0.0 + vit_embeds` (modeling_internvl_sam.py:124-158): table_grad [V, D] (out_dtype 0 fp32 / 1 bf16, rounded
+ * once from the fp32 sum) = sum of the dX rows [rows, ldx] of each id; rows whose id is padding_idx or whose skip[] entry is nonzero (skip may be NULL)
+ * contribute nothing, ids outside [0, V) are ignored, rows no id names are zero; D % 4 == 0, D <= 8192.  sorted_ids / order = a STABLE sort of the ids and the positions they came
+ * from (the caller's torch.sort(stable=True)): each id's rows are summed in ascending position order -- no atomics, two runs give the same bits. */
+int ullsam_train_embedding_bwd(const float* dx, long ldx, const int* sorted_ids, const int* order, const int* skip, long rows, int D, int V, int padding_idx,
+                               void* table_grad, int out_dtype, void* stream);
 /* dst[idx[r]] += src[r]: gradient of the point-label embedding table (prompt_encoder.py:76-96) */
 int ullsam_train_index_add_rows(const float* src, const int* idx, float* dst, long rows, int C, int nrows_dst, void* stream);
 

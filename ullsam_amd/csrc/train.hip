@@ -968,9 +968,10 @@ extern "C" int ullsam_train_attn_rows(float* S, float* dP, const float* bias_h, 
     return 0;
 }
 
-// ---- RMSNorm backward (modeling_internlm2.py:75-89): y = x * rsqrt(mean(x^2) + eps) * w; one wave per row; dw (optional) by atomics ------
+// ---- RMSNorm backward (modeling_internlm2.py:75-89): y = x * rsqrt(mean(x^2) + eps) * w; one wave per row; dw_rows (optional) = the rows of
+// dy * xhat, whose column sums (ullsam_train_colsum, in order: no atomics) are dw ------
 __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ dy,
-                                                          float* __restrict__ dx, float* __restrict__ dw, long rows, int D, float eps) {
+                                                          float* __restrict__ dx, float* __restrict__ dw_rows, long rows, int D, float eps) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -985,14 +986,14 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const float* __restric
     for (int i = lane; i < D; i += 64) {
         const float xh = xr[i] * rstd;
         dx[row * D + i] = rstd * (gr[i] * w[i] - xh * mgx);
-        if (dw) atomicAdd(dw + i, gr[i] * xh);
+        if (dw_rows) dw_rows[row * D + i] = gr[i] * xh;
     }
 }
 // The same backward with one WORKGROUP per row and the row held in registers (D % 4 == 0, D <= 1024 VPT = 4096): x and dy * w are fetched once as float4 (the kernel above walks the
 // row three times with 4-byte loads from one wave: 70 us for 1081 x 4096, latency-bound at one wave per SIMD); sums: wave, then the four waves in order.
 template <int VPT>
 __global__ __launch_bounds__(256) void rmsnorm_bwd_row_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ dy,
-                                                              float* __restrict__ dx, float* __restrict__ dw, int D, float eps) {
+                                                              float* __restrict__ dx, float* __restrict__ dw_rows, int D, float eps) {
     __shared__ float red[2][4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long row = blockIdx.x;
@@ -1027,20 +1028,20 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_row_kernel(const float* __res
         if (i >= D) continue;
         const float4 xh = make_float4(xv[j].x * rstd, xv[j].y * rstd, xv[j].z * rstd, xv[j].w * rstd);
         *reinterpret_cast<float4*>(dx + row * D + i) = make_float4(rstd * (gv[j].x - xh.x * mgx), rstd * (gv[j].y - xh.y * mgx), rstd * (gv[j].z - xh.z * mgx), rstd * (gv[j].w - xh.w * mgx));
-        if (dw) {   // (dw = sum_rows dy * xhat: dy = gv / w is not kept -- re-read)
+        if (dw_rows) {   // (dw = sum_rows dy * xhat: dy = gv / w is not kept -- re-read)
             const float4 g = *reinterpret_cast<const float4*>(gr + i);
-            atomicAdd(dw + i, g.x * xh.x); atomicAdd(dw + i + 1, g.y * xh.y); atomicAdd(dw + i + 2, g.z * xh.z); atomicAdd(dw + i + 3, g.w * xh.w);
+            *reinterpret_cast<float4*>(dw_rows + row * D + i) = make_float4(g.x * xh.x, g.y * xh.y, g.z * xh.z, g.w * xh.w);
         }
     }
 }
-extern "C" int ullsam_train_rmsnorm_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, long rows, int D, float eps, void* stream) {
+extern "C" int ullsam_train_rmsnorm_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw_rows, long rows, int D, float eps, void* stream) {
     ULLSAM_CHECK(rows > 0 && D > 0, "train_rmsnorm_bwd: rows=%ld D=%d", rows, D);
-    if (D % 4 == 0 && D <= 4096 && rows < (1l << 31) && ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)dy | (uintptr_t)dx)) & 15) == 0) {   // (the widths ullsam_norm's forward takes)
-        rmsnorm_bwd_row_kernel<4><<<dim3((unsigned)rows), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(x, w, dy, dx, dw, D, eps);
+    if (D % 4 == 0 && D <= 4096 && rows < (1l << 31) && ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)dw_rows)) & 15) == 0) {   // (the widths ullsam_norm's forward takes)
+        rmsnorm_bwd_row_kernel<4><<<dim3((unsigned)rows), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(x, w, dy, dx, dw_rows, D, eps);
         ULLSAM_LAUNCH_CHECK();
         return 0;
     }
-    rmsnorm_bwd_kernel<<<dim3((unsigned)((rows + 3) / 4)), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(x, w, dy, dx, dw, rows, D, eps);
+    rmsnorm_bwd_kernel<<<dim3((unsigned)((rows + 3) / 4)), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(x, w, dy, dx, dw_rows, rows, D, eps);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -1322,6 +1323,130 @@ extern "C" int ullsam_train_cross_entropy_bwd(const float* logits, long ld, cons
                                               long ldx, long rows, int V, void* stream) {
     ULLSAM_CHECK(rows > 0 && rows < 65536 && V > 0 && ld >= V && ldx >= V, "train_cross_entropy_bwd: rows=%ld V=%d ld=%ld ldx=%ld", rows, V, ld, ldx);
     ce_bwd_kernel<<<dim3((unsigned)((ldx + 255) / 256), (unsigned)rows), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(logits, ld, labels, lse, out2, gscale, dlogits, ldx, V);
+    ULLSAM_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- The LM-loss gradient in the head GEMMs' own operand layouts (a trainable head: modeling_internlm2.py:1081-1096 under train.py:284-318): the value of
+// ce_bwd_kernel, (softmax - onehot) * g / #labelled, rounded once to bf16 (round to nearest even) and written in one pass over the logits as
+//   dlog  [rows, ldd] row-major (the A operand of dX = dlog W), columns V .. Vp - 1 zero, and
+//   dlogT [Vp, ldt] (the A operand of dW = dlog^T h), rows V .. Vp - 1 and columns rows .. Rp - 1 zero;
+// Vp / Rp = V / rows rounded up to 64.  One workgroup per 64 x 64 tile: a wave reads one 256-byte row of logits, the transposed copy goes out through LDS.
+__global__ __launch_bounds__(256) void ce_bwd_bf16_kernel(const float* __restrict__ x, long ld, const long long* __restrict__ labels, const float* __restrict__ lse,
+                                                          const float* __restrict__ mean_out, const float* __restrict__ g, bf16* __restrict__ dlog, long ldd,
+                                                          bf16* __restrict__ dlogT, long ldt, long R, int V) {
+    __shared__ float tile[64][65];
+    const int c = threadIdx.x & 63, rg = threadIdx.x >> 6;
+    const long r0 = (long)blockIdx.y * 64;
+    const int j = blockIdx.x * 64 + c;
+    const float scale = g[0] * mean_out[1];
+#pragma unroll 4
+    for (int i = rg; i < 64; i += 4) {
+        const long r = r0 + i;
+        float d = 0.f;
+        if (r < R) {
+            const long long lab = labels[r];
+            if (j < V && lab >= 0 && lab < V) d = (__expf(x[r * ld + j] - lse[r]) - (j == lab ? 1.f : 0.f)) * scale;
+        }
+        const bf16 b = (bf16)d;
+        if (dlog != nullptr && r < R) dlog[r * ldd + j] = b;
+        tile[i][c] = (float)b;
+    }
+    if (dlogT == nullptr) return;
+    __syncthreads();
+    const long jt0 = (long)blockIdx.x * 64;
+#pragma unroll 4
+    for (int i = rg; i < 64; i += 4) dlogT[(jt0 + i) * ldt + r0 + c] = (bf16)tile[c][i];
+}
+extern "C" int ullsam_train_cross_entropy_bwd_bf16(const float* logits, long ld, const long long* labels, const float* lse, const float* out2, const float* gscale,
+                                                   void* dlog, long ldd, void* dlogT, long ldt, long rows, int V, void* stream) {
+    const long Vp = ((long)V + 63) / 64 * 64, Rp = (rows + 63) / 64 * 64;
+    ULLSAM_CHECK(rows > 0 && rows < (1L << 30) && V > 0 && ld >= V && (dlog != nullptr || dlogT != nullptr) && (dlog == nullptr || ldd >= Vp) && (dlogT == nullptr || ldt >= Rp),
+                 "train_cross_entropy_bwd_bf16: rows=%ld V=%d ld=%ld ldd=%ld ldt=%ld (ldd >= V rounded up to 64, ldt >= rows rounded up to 64)", rows, V, ld, ldd, ldt);
+    ce_bwd_bf16_kernel<<<dim3((unsigned)(Vp / 64), (unsigned)(Rp / 64)), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+        logits, ld, labels, lse, out2, gscale, reinterpret_cast<bf16*>(dlog), ldd, reinterpret_cast<bf16*>(dlogT), ldt, rows, V);
+    ULLSAM_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- The gradient of nn.Embedding(V, D, padding_idx) (InternLM2's tok_embeddings, modeling_internlm2.py:808,815) behind the <IMG_CONTEXT> splice of
+// modeling_internvl_sam.py:124-158 (those positions are `* 0.0`: they contribute nothing).  Deterministic, no atomics: the caller hands over a STABLE sort of
+// the ids (sorted ids + the positions they came from), so the rows of one id form a segment in ascending position order.  Two launches:
+//   a zero fill of the [V, D] table (16-byte stores), then one workgroup per sorted position -- the head of each segment (its first entry) sums the segment's
+//   rows in order, lanes across D (<= 8192) with 16-byte loads, and writes the row once (fp32, or bf16 rounded once from the fp32 sum); every other workgroup exits.
+// Cost: one pass over the table plus one read of each dX row.
+__global__ __launch_bounds__(256) void zero_fill16_kernel(uint4* __restrict__ p, long n16) {
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n16; i += (long)gridDim.x * 256) p[i] = z;
+}
+// (the segment's positions go through LDS 256 at a time, read by all lanes at once -- walked one dependent load at a time, the 1024 masked <IMG_CONTEXT> positions of a
+// prompt cost ~0.4 ms; the row is held in registers, NC float4 per lane, so the segment is walked once)
+template <typename T, int NC>
+__global__ __launch_bounds__(256) void embedding_bwd_kernel(const float* __restrict__ dx, long ldx, const int* __restrict__ sid, const int* __restrict__ order,
+                                                            const int* __restrict__ skip, long rows, int D, int V, int padding_idx, T* __restrict__ out) {
+    __shared__ int srow[256];
+    const long s = blockIdx.x;
+    const int id = sid[s];
+    if (id < 0 || id >= V || id == padding_idx || (s > 0 && sid[s - 1] == id)) return;
+    const int t = threadIdx.x;
+    float4 a[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) a[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (long base = s;; base += 256) {
+        const long k = base + t;
+        const bool in = k < rows && sid[k] == id;             // the segment is a prefix of every chunk (sorted ids)
+        int r = -1;
+        if (in) {
+            r = order[k];
+            if (skip != nullptr && skip[r] != 0) r = -1;
+        }
+        srow[t] = r;
+        const int n = __syncthreads_count(in);
+        for (int j = 0; j < n; ++j) {
+            const int rr = srow[j];
+            if (rr < 0) continue;
+            const float* src = dx + (long)rr * ldx;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const int col = 4 * (t + 256 * c);
+                if (col < D) {
+                    const float4 v = load4(src + col);
+                    a[c].x += v.x; a[c].y += v.y; a[c].z += v.z; a[c].w += v.w;
+                }
+            }
+        }
+        if (n < 256) break;
+        __syncthreads();                                      // (srow is rewritten by the next chunk)
+    }
+    T* orow = out + (long)id * D;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int col = 4 * (t + 256 * c);
+        if (col < D) store4(orow + col, a[c]);
+    }
+}
+template <typename T>
+static void embedding_bwd_launch(const float* dx, long ldx, const int* sid, const int* order, const int* skip, long rows, int D, int V, int padding_idx, T* out, hipStream_t st) {
+    const dim3 g((unsigned)rows);
+    if (D <= 1024) embedding_bwd_kernel<T, 1><<<g, 256, 0, st>>>(dx, ldx, sid, order, skip, rows, D, V, padding_idx, out);
+    else if (D <= 2048) embedding_bwd_kernel<T, 2><<<g, 256, 0, st>>>(dx, ldx, sid, order, skip, rows, D, V, padding_idx, out);
+    else if (D <= 4096) embedding_bwd_kernel<T, 4><<<g, 256, 0, st>>>(dx, ldx, sid, order, skip, rows, D, V, padding_idx, out);
+    else embedding_bwd_kernel<T, 8><<<g, 256, 0, st>>>(dx, ldx, sid, order, skip, rows, D, V, padding_idx, out);
+}
+extern "C" int ullsam_train_embedding_bwd(const float* dx, long ldx, const int* sorted_ids, const int* order, const int* skip, long rows, int D, int V,
+                                          int padding_idx, void* table_grad, int out_dtype, void* stream) {
+    const int es = out_dtype == ULLSAM_DT_BF16 ? 2 : 4;
+    ULLSAM_CHECK(rows > 0 && rows < (1L << 31) && D > 0 && D % 4 == 0 && D <= 8192 && ldx >= D && ldx % 4 == 0 && V > 0 && (out_dtype == ULLSAM_DT_F32 || out_dtype == ULLSAM_DT_BF16)
+                 && ((long)V * D * es) % 16 == 0 && (reinterpret_cast<unsigned long>(table_grad) & 15) == 0 && (reinterpret_cast<unsigned long>(dx) & 15) == 0,
+                 "train_embedding_bwd: rows=%ld D=%d ldx=%ld V=%d dtype=%d (D, ldx % 4 == 0, D <= 8192; 16-byte aligned dX and table)", rows, D, ldx, V, out_dtype);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const long n16 = (long)V * D * es / 16;
+    zero_fill16_kernel<<<dim3((unsigned)min(8192L, (n16 + 255) / 256)), 256, 0, st>>>(reinterpret_cast<uint4*>(table_grad), n16);
+    ULLSAM_LAUNCH_CHECK();
+    if (out_dtype == ULLSAM_DT_BF16)
+        embedding_bwd_launch<bf16>(dx, ldx, sorted_ids, order, skip, rows, D, V, padding_idx, reinterpret_cast<bf16*>(table_grad), st);
+    else
+        embedding_bwd_launch<float>(dx, ldx, sorted_ids, order, skip, rows, D, V, padding_idx, reinterpret_cast<float*>(table_grad), st);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }

@@ -122,7 +122,7 @@ class InternVLSAMModel(Packed):
             raise NotImplementedError("tuple outputs are not provided; use return_dict=True (what app.py / train_joint_v2.py pass)")
         from .. import training
         if training.wants_autograd(self) and past_key_values is None and position_ids is None:
-            # train() mode with gradients on (train_joint_v2.py:988-998): mlp1 -> frozen LLM -> mlp2 as an autograd graph over HIP kernels
+            # train() mode with gradients on (train_joint_v2.py:988-998, train.py:284-318): mlp1 -> LLM (frozen or trainable) -> mlp2 as an autograd graph over HIP kernels
             return training.composite_forward(self, pixel_values, input_ids, attention_mask, labels, output_hidden_states)
         with torch.no_grad():
             return self._forward_inference(pixel_values, input_ids, attention_mask, position_ids, image_flags, past_key_values, labels, use_cache,

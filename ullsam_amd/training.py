@@ -1,7 +1,7 @@
 """Training: the differentiable part of one step of the reference's trainer (train_joint_v2.py:943-1100).
 
     loss, bce, dice = train_step_loss(model, pixel_values, input_ids, attention_mask, (coords, labels), gt_masks)
-    loss.backward()        # .grad of vision_model / mlp1 / mlp2 / prompt_encoder / mask_decoder parameters (the LLM is frozen)
+    loss.backward()        # .grad of the vision_model / mlp1 / mlp2 / prompt_encoder / mask_decoder (and language_model) parameters that require it
 
 is the drop-in for
 
@@ -12,8 +12,10 @@ is the drop-in for
     loss, bce, dice, _ = calc_instance_loss(F.interpolate(low, (S, S), mode="bilinear", align_corners=False), gt, BCELoss(), DiceLoss())
 
 built from three pieces that can be used on their own: `vision_feature_rows` (the vision model), `llm_image_hidden` (pixel_shuffle, mlp1, the
-frozen LLM) and `segmentation_loss` (mlp2, prompt encoder, mask decoder, upsample, BCE + Dice).  Supported `trainable_modules`
-(train_joint_v2.py:1280-1359): "vision_model", "mlp1", "mlp2", "prompt_encoder", "mask_decoder" -- everything the reference trains.  The
+LLM) and `segmentation_loss` (mlp2, prompt encoder, mask decoder, upsample, BCE + Dice).  Supported `trainable_modules`
+(train_joint_v2.py:1280-1359): "vision_model", "mlp1", "language_model", "mlp2", "prompt_encoder", "mask_decoder"; and the caption trainer's SFT
+stage (train.py:284-318, 400-480: `.loss` of the composite's forward into mlp1 and the whole LLM -- token embeddings, decoder layers, final norm,
+LM head).  The
 arithmetic is fp32; the model may be fp32 or bf16 (bf16 parameters are widened on use and receive bf16 gradients).  One image per step.
 
 Every arithmetic step, forward and backward, is a HIP kernel (csrc/train.hip for the backward kernels, the generic fp32 matmul and the
@@ -125,7 +127,7 @@ RECOMPUTE_P = True   # matrix-form attention keeps q, k, v and rebuilds the prob
 MATRIX_ATTN_FROM = 0         # attention through materialised score matrices from Sq * Sk >= this; below it one workgroup per query, whose backward adds dk / dv by
 #                              atomics (order-dependent sums): 0 keeps every attention on the matrix form, so that two runs of a step are bit-equal
 FUSED_GLOBAL_FWD = True   # bf16 models: the forward value of the ViT's attention blocks (global and windowed) comes from the inference path's kernels on the packed qkv; the backward stays the matrix form
-FUSED_CAUSAL_FWD = True   # bf16 models: the frozen LLM's attention FORWARD runs on the inference path's causal kernel (no score matrix); the backward stays the matrix form
+FUSED_CAUSAL_FWD = True   # bf16 models: the LLM's attention FORWARD runs on the inference path's causal kernel (no score matrix); the backward stays the matrix form
 FUSED_CAST_TRANSPOSE = True   # LinearBf16Fn: x -> (bf16 x, x^T) and dY -> (bf16 dY, dY^T, column sums) each in one pass (ops.cast_transpose_bf16); False: separate cast / transpose / column-sum launches
 INPLACE_ATTN = True  # the ViT / LLM attention products read q / k / v / dO and write out / dq / dk / dv inside the row tensors (ullsam_train_matmul_heads); False: head-major copies around plain batched products (tests / A-B)
 MFMA_LINEAR = True   # nn.Linear forward / backward on the fp32 MFMA GEMM of the inference path where its shapes allow (inner dimension % 32 == 0);
@@ -321,7 +323,8 @@ def _apply_linear(x, w, b):
 
 
 def _frozen_linear(x, w, b):
-    """nn.Linear with a frozen weight inside llm_image_hidden: bf16 weights take the bf16 GEMM, fp32 weights the fp32 path."""
+    """nn.Linear of the LLM inside llm_image_hidden: frozen bf16 weights take FrozenLinearBf16Fn (no weight gradient; the only user of `splitk_ok`),
+    trainable weights (SFT, "language_model") and fp32 weights take _apply_linear -- LinearBf16Fn / LinearFn, which return dW."""
     if w.dtype == torch.bfloat16 and not w.requires_grad and w.shape[1] % 64 == 0 and w.shape[0] % 64 == 0:
         return FrozenLinearBf16Fn.apply(x, w, b)
     return _apply_linear(x, w, b)
@@ -715,9 +718,9 @@ class RMSNormFn(Function):
         x, w = ctx.saved_tensors
         rows, D = x.shape
         dx = torch.empty_like(x)
-        dw = torch.zeros_like(w) if ctx.needs_input_grad[1] else None
-        _lib.call("ullsam_train_rmsnorm_bwd", x.data_ptr(), w.data_ptr(), _c(dy).data_ptr(), dx.data_ptr(), ops._p(dw), rows, D, float(ctx.eps), _s())
-        return dx, dw, None
+        dw_rows = torch.empty_like(x) if ctx.needs_input_grad[1] else None      # a trainable weight (the LLM's norms under SFT): dy * xhat rows, summed in order
+        _lib.call("ullsam_train_rmsnorm_bwd", x.data_ptr(), w.data_ptr(), _c(dy).data_ptr(), dx.data_ptr(), ops._p(dw_rows), rows, D, float(ctx.eps), _s())
+        return dx, (None if dw_rows is None else _colsum(dw_rows)), None
 
 
 class RoPEFn(Function):
@@ -873,9 +876,12 @@ class LMLossFn(Function):
     """The language-model loss of InternLM2ForCausalLM.forward (modeling_internlm2.py:1081-1096) on hidden rows: logits = output(h).float() on the inference
     path's GEMM (bf16 weights: bf16 MFMA, fp32 weights: exact-fp32 MFMA), CrossEntropyLoss() over them (labels == -100 ignored, mean over the others; HIP
     kernels, ordered sums).  The [rows, 92553] logits are NOT kept (400 MB per image): the backward rebuilds them, forms (softmax - onehot) / #labelled in a
-    zero-padded [rows, V rounded up to 64] buffer and multiplies by the head's weight.  The head is frozen in every setting of the reference's trainer
-    (setup_model_params, train_joint_v2.py:1280-1359): it receives no gradient here.  The trainer's segmentation branch adds this loss as `0 * loss`
-    (:1096): an incoming gradient of exactly zero returns zeros without the two GEMMs (one scalar read back per step)."""
+    zero-padded [rows, V rounded up to 64] buffer and multiplies by the head's weight.
+    A frozen head (the joint trainer without "language_model") receives no gradient.  A trainable one (the SFT stage, train.py:400-480, or
+    --trainable_modules language_model) gets dW = dlog^T h: bf16 heads keep h's bf16 copy AND its transpose from one pass (ops.cast_transpose_bf16, as
+    LinearBf16Fn), and the backward writes dlog in bf16 in both GEMM layouts at once (ullsam_train_cross_entropy_bwd_bf16); fp32 heads take the exact-fp32
+    product.  The joint trainer's segmentation branch adds this loss as `0 * loss` (:1096): an incoming gradient of exactly zero returns zeros without the
+    GEMMs (one scalar read back per step) -- for a trainable head a zero dW tensor, as the reference's autograd leaves one (AdamW's weight decay then acts on it)."""
 
     @staticmethod
     def _logits(h, w):
@@ -888,16 +894,27 @@ class LMLossFn(Function):
         h = _c(h)
         labels = labels.to(torch.int64).contiguous()
         R, V = h.shape[0], w.shape[0]
-        logits = LMLossFn._logits(h, w)
+        ctx.train_w = ctx.needs_input_grad[1]
+        ctx.bf16_w = BF16_LINEAR and ctx.train_w and w.dtype == torch.bfloat16 and h.shape[1] % 64 == 0
+        if ctx.bf16_w:           # trainable bf16 head: h leaves one pass as the logits GEMM's bf16 operand and as the h^T the dW product reads
+            hb, ht, _ = ops.cast_transpose_bf16(h, 64)
+            logits = ops.gemm(hb, w.detach(), None, out_f32=True)
+        else:
+            logits = LMLossFn._logits(h, w)
         lse = torch.empty((R,), dtype=F32, device=h.device)
         rows = torch.empty((R,), dtype=F32, device=h.device)
         out2 = torch.empty((2,), dtype=F32, device=h.device)
         _lib.call("ullsam_train_cross_entropy", logits.data_ptr(), V, labels.data_ptr(), lse.data_ptr(), rows.data_ptr(), out2.data_ptr(), R, V, _s())
-        ctx.save_for_backward(h, w, labels, lse, out2)
+        if ctx.bf16_w:
+            ctx.save_for_backward(hb, w, labels, lse, out2, ht)
+        else:
+            ctx.save_for_backward(h, w, labels, lse, out2)
         return out2[0].clone()
 
     @staticmethod
     def backward(ctx, dl):
+        if ctx.train_w:
+            return LMLossFn._backward_trainable(ctx, dl)
         h, w, labels, lse, out2 = ctx.saved_tensors
         if float(dl) == 0.0:                                  # `0 * loss + seg_loss`: the gradient is exactly zero
             return torch.zeros_like(h), None, None
@@ -916,14 +933,81 @@ class LMLossFn(Function):
             _mm(dlog, _c(w.detach()).float() if w.dtype != F32 else _c(w.detach()), dx, R, D, V, (0, Vp, 1), (0, D, 1), (0, D, 1))
         return dx, None, None
 
+    @staticmethod
+    def _backward_trainable(ctx, dl):
+        """dX = dlog W and dW = dlog^T h.  bf16 head: both products on the bf16 MFMA GEMM (fp32 results) from the bf16 dlog / dlog^T that
+        ullsam_train_cross_entropy_bwd_bf16 writes in one pass; otherwise the fp32 dlog and the exact-fp32 products."""
+        want_x = ctx.needs_input_grad[0]
+        if ctx.bf16_w:
+            hb, w, labels, lse, out2, ht = ctx.saved_tensors
+        else:
+            h, w, labels, lse, out2 = ctx.saved_tensors
+            hb = h
+        R, D = hb.shape
+        V = w.shape[0]
+        dx = dw = None
+        if float(dl) == 0.0:                                  # `0 * loss + seg_loss`: zeros, and a zero dW tensor rather than none
+            return (torch.zeros((R, D), dtype=F32, device=hb.device) if want_x else None), torch.zeros_like(w), None
+        Vp = -(-V // 64) * 64
+        g = _c(dl).reshape(1).to(F32)
+        if ctx.bf16_w:
+            logits = ops.gemm(hb, w.detach(), None, out_f32=True)
+            Rp = ht.shape[1]
+            dlog = torch.empty((R, Vp), dtype=torch.bfloat16, device=hb.device) if want_x else None
+            dlogt = torch.empty((Vp, Rp), dtype=torch.bfloat16, device=hb.device)
+            _lib.call("ullsam_train_cross_entropy_bwd_bf16", logits.data_ptr(), V, labels.data_ptr(), lse.data_ptr(), out2.data_ptr(), g.data_ptr(),
+                      ops._p(dlog), Vp, dlogt.data_ptr(), Rp, R, V, _s())
+            del logits
+            if want_x:
+                dx = ops.gemm(dlog, ops.transpose_to_bf16(w.detach(), 64), out_f32=True)        # [R, Vp] x ([D, Vp])^T; W^T's pad columns are zeros
+                del dlog
+            dw = ops.gemm(dlogt, ht, out_f32=True)[:V]                                        # [Vp, Rp] x ([D, Rp])^T; the pad rows / columns are zeros
+            return dx, dw, None
+        logits = LMLossFn._logits(hb, w)
+        dlog = torch.empty((R, Vp), dtype=F32, device=hb.device)
+        _lib.call("ullsam_train_cross_entropy_bwd", logits.data_ptr(), V, labels.data_ptr(), lse.data_ptr(), out2.data_ptr(), g.data_ptr(), dlog.data_ptr(), Vp, R, V, _s())
+        del logits
+        wf = _c(w.detach())
+        if want_x:
+            dx = torch.empty((R, D), dtype=F32, device=hb.device)
+            _mm(dlog, wf, dx, R, D, V, (0, Vp, 1), (0, D, 1), (0, D, 1))                      # dX [R, D] = dlog [R, V] W [V, D]
+        dw = torch.empty((V, D), dtype=F32, device=hb.device)
+        _mm(dlog, hb, dw, V, D, R, (0, 1, Vp), (0, D, 1), (0, D, 1))                           # dW [V, D] = dlog^T [V, R] h [R, D]
+        return dx, dw, None
+
+
+class EmbeddingFn(Function):
+    """The token-embedding gather of a TRAINABLE table (modeling_internlm2.py:808,815: nn.Embedding(V, D, padding_idx=pad_token_id)) -> fp32 rows.
+    Backward: the dense [V, D] table gradient (ullsam_train_embedding_bwd, in the table's dtype): rows of the padding id and the `skip` positions (the
+    <IMG_CONTEXT> splice, whose embeddings enter as `* 0.0`, modeling_internvl_sam.py:124-158) contribute nothing; each id's rows are summed in position
+    order over a stable sort of the ids (torch.sort: data movement) -- two runs give the same bits."""
+
+    @staticmethod
+    def forward(ctx, w, ids, skip, padding_idx):
+        ctx.save_for_backward(ids, skip)
+        ctx.shape, ctx.dtype = w.shape, w.dtype
+        ctx.padding_idx = -1 if padding_idx is None else int(padding_idx)
+        return w.detach()[ids].float()
+
+    @staticmethod
+    def backward(ctx, dy):
+        ids, skip = ctx.saved_tensors
+        V, D = ctx.shape
+        dy = _c(dy)
+        sid, order = torch.sort(ids.to(torch.int32), stable=True)
+        order = order.to(torch.int32)
+        dt = torch.empty((V, D), dtype=ctx.dtype, device=dy.device)
+        _lib.call("ullsam_train_embedding_bwd", dy.data_ptr(), D, sid.data_ptr(), order.data_ptr(), ops._p(skip), ids.numel(), D, V, ctx.padding_idx,
+                  dt.data_ptr(), 1 if ctx.dtype == torch.bfloat16 else 0, _s())
+        return dt, None, None, None
+
 
 def lm_loss(lm, hidden_all: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-    """`.loss` of the reference's forward as a differentiable scalar (see LMLossFn): hidden_all [B, S, D] carries the graph (mlp1 through the frozen LLM);
+    """`.loss` of the reference's forward as a differentiable scalar (see LMLossFn): hidden_all [B, S, D] carries the graph (mlp1 through the LLM; the head's
+    weight when it requires grad);
     shift_logits = logits[..., :-1, :] against labels[..., 1:]: the last position's logits are never formed."""
     B, S, D = hidden_all.shape
     w = lm.output.weight
-    if w.requires_grad:
-        raise NotImplementedError("a trainable LM head: the reference's trainer freezes the language model in every setting (train_joint_v2.py:1280-1359)")
     h = hidden_all[:, :-1].reshape(B * (S - 1), D)
     lab = labels[:, 1:].reshape(-1)
     if not lab.is_cuda:   # host labels (what the trainer's collate hands over): torch's CrossEntropyLoss raises on a label outside {-100} U [0, V) -- checked here, where it costs no device sync
@@ -1055,12 +1139,13 @@ def segmentation_loss(model, llm_hidden: torch.Tensor, image_embeddings: Optiona
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
-# Second slice: the projector mlp1 and the (frozen) LLM between the vision features and the hidden states the first slice starts from.
+# Second slice: the projector mlp1 and the LLM (frozen or trainable) between the vision features and the hidden states the first slice starts from.
 def llm_image_hidden(model, vit_feature_rows: torch.Tensor, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                      return_all: bool = False):
-    """The LLM's last hidden state over the image tokens, differentiable with respect to `mlp1` (and to the vision features):
-    extract_feature's pixel_shuffle + mlp1 (modeling_internvl_sam.py:226-251), the image-token splice of forward (:136-158), InternLM2's
-    layers (modeling_internlm2.py:598-618, 345-419, 75-89; frozen weights receive no gradient work) and the image-token slice of :195-205.
+    """The LLM's last hidden state over the image tokens, differentiable with respect to `mlp1` (and to the vision features) and to every LLM
+    parameter that requires grad: extract_feature's pixel_shuffle + mlp1 (modeling_internvl_sam.py:226-251), the image-token splice of forward
+    (:136-158; a trainable token-embedding table goes through EmbeddingFn), InternLM2's layers (modeling_internlm2.py:598-618, 345-419, 75-89;
+    frozen weights receive no gradient work, trainable ones take LinearBf16Fn / LinearFn / RMSNormFn's dW) and the image-token slice of :195-205.
     vit_feature_rows fp32 [B, 64*64, 256] = the vision model's output as NHWC rows (a constant here: the reference computes it under
     no_grad, :243-244); input_ids [B, S] with the <IMG_CONTEXT> run; returns [B, n_img_tokens, D_llm]."""
     lm = model.language_model
@@ -1084,7 +1169,11 @@ def llm_image_hidden(model, vit_feature_rows: torch.Tensor, input_ids: torch.Ten
     n_sel = int(sel.sum())
     if n_sel != vit_embeds.shape[0]:
         raise ValueError(f"{n_sel} <IMG_CONTEXT> tokens for {vit_embeds.shape[0]} image embeddings")
-    x = lm.model.tok_embeddings.weight.detach()[ids].float().clone()             # frozen embedding rows (a gather)
+    emb = lm.model.tok_embeddings
+    if emb.weight.requires_grad:                                                 # trainable table: its gradient skips the padding id and the spliced positions
+        x = EmbeddingFn.apply(emb.weight, ids, sel.to(torch.int32), emb.padding_idx)
+    else:
+        x = emb.weight.detach()[ids].float().clone()                             # frozen embedding rows (a gather)
     x = x.index_put((sel.nonzero(as_tuple=True)[0],), vit_embeds)                # input_embeds[selected] = vit_embeds  (:150-152)
     H, KVH = cfg.num_attention_heads, cfg.num_key_value_heads
     hd, G = cfg.hidden_size // H, H // KVH
@@ -1322,7 +1411,8 @@ def mask_decoder_forward(md, image_embeddings, image_pe, sparse_prompt_embedding
 
 def composite_forward(model, pixel_values, input_ids, attention_mask=None, labels=None, output_hidden_states=None):
     """InternVLSAMModel.forward with gradients (modeling_internvl_sam.py:106-224 as train_joint_v2.py:988-998 calls it): the vision model runs
-    without gradients here, as in the reference (extract_feature, :243-244); mlp1 -> frozen LLM -> mlp2 is differentiable; `.loss` is the
+    without gradients here, as in the reference (extract_feature, :243-244); mlp1 -> LLM -> mlp2 is differentiable (the LLM's own parameters too where they
+    require grad: train.py's SFT stage, train_joint_v2.py's "language_model"); `.loss` is the
     language-model loss of the reference's forward (differentiable: `lm_loss`); `.hidden_states` is the dense feature [B, 256, 64, 64] the segmentation
     branch continues from.  `image_flags` / `position_ids` of the reference's signature do not enter this path (the reference ignores image_flags too, :119-135)."""
     from .modeling.outputs import CausalLMOutputWithPast
@@ -1337,7 +1427,7 @@ def composite_forward(model, pixel_values, input_ids, attention_mask=None, label
     logits_fn = lambda: lm.lm_head(hidden_all.detach())
     if labels is not None:
         # `.loss` is differentiable, as in the reference: its trainer's other branch (train_joint_v2.py: masks is None or use_llm_hidden_states False) back-propagates
-        # `outputs.loss` into mlp1 through the frozen LLM; in the segmentation branch the loss enters as 0 * loss (:1096) and its backward costs one head GEMM pair
+        # `outputs.loss` into mlp1 through the LLM; in the segmentation branch the loss enters as 0 * loss (:1096) and its backward costs no GEMM
         loss = lm_loss(lm, hidden_all, labels)
     hs = None
     if output_hidden_states:
