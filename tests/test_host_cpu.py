@@ -705,3 +705,14 @@ def test_sampling_distribution_equals_the_logits_warpers_of_transformers():
             n = min(na, nb)
             assert np.abs(a[:n] / a[:n].sum() - b[:n] / b[:n].sum()).max() < 1e-5, (T, k, p, r)
             assert abs(got[r].sum() - 1.0) < 1e-5
+
+
+def test_every_training_entry_point_is_named_by_a_test():
+    """Each ullsam_train_* entry point of include/ullsam_hip.h is called by name in some test module (tests/test_train_kernels_gpu.py checks them
+    against float64 definitions), so a new training kernel cannot arrive without a test that reaches it directly."""
+    names = [s for s in _header_symbols() if s.startswith("ullsam_train_")]
+    assert len(names) >= 20
+    here = os.path.join(ROOT, "tests")
+    text = "".join(open(os.path.join(here, f)).read() for f in sorted(os.listdir(here)) if f.startswith("test_") and f.endswith(".py"))
+    missing = [s for s in names if not re.search(r"\b" + s + r"\b", text)]
+    assert not missing, f"training entry points no test names: {missing}"

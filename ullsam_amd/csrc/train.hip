@@ -21,7 +21,8 @@ struct MmArgs {
     int bin, a_div, b_div;
     long a_h, b_h, c_h;
     // causal structure of a square attention (Sq == Sk, key j visible to query i iff j <= i), MFMA kernels only: 1 = C[m = query][n = key]: tiles with every key behind every query are
-    // not formed (the row pass does not read masked entries and writes zeros there); 2 = the sum runs over queries and m is the key: queries before the tile's first key meet zeros,
+    // not formed (the row pass reads no entry behind the diagonal where P is 0 and writes zeros there; a row whose visible keys are all padded has P != 0 behind the diagonal, so
+    // a batch with such rows does not use tri); 2 = the sum runs over queries and m is the key: queries before the tile's first key meet zeros,
     // start at it; 3 = the sum runs over keys and m is the query: keys behind the tile's last query meet zeros, stop after it.  0 elsewhere.
     int tri;
 };
@@ -836,7 +837,8 @@ __global__ __launch_bounds__(256) void attn_rows_bwd_kernel(float* __restrict__ 
     for (int kt = tid; kt < Sk; kt += 256) {
         const float pj = s[kt] * inv;
         s[kt] = pj;
-        if (causal >= 0 && kt > qi + causal) g[kt] = 0.f;        // (dP behind the diagonal may never have been written)
+        if (causal >= 0 && kt > qi + causal && pj == 0.f) g[kt] = 0.f;   // (dP behind the diagonal may never have been written; it is read only where P is not 0:
+                                                                          //  a row whose visible keys are all padded, uniform over every single-masked entry)
         ds += pj * g[kt];
     }
     const float D = block_reduce(ds, false);
@@ -918,7 +920,7 @@ __global__ __launch_bounds__(256) void attn_rows_reg_kernel(float* __restrict__ 
     if (!dP) return;
     float gr[VPT], ds = 0.f;
 #pragma unroll
-    for (int i = 0; i < VPT; ++i) { const int kt = tix + T * i; gr[i] = (live && kt < Sk && !(causal >= 0 && kt > qi + causal)) ? g[kt] : 0.f; ds += p[i] * gr[i]; }
+    for (int i = 0; i < VPT; ++i) { const int kt = tix + T * i; gr[i] = (live && kt < Sk && (p[i] != 0.f || !(causal >= 0 && kt > qi + causal))) ? g[kt] : 0.f; ds += p[i] * gr[i]; }
     const float D = row_reduce(ds, false);
     float* mine = rows_lds + rib * (T * VPT);
 #pragma unroll

@@ -94,12 +94,19 @@ def _mmh(A, B, C, M, N, K, outer, heads, sa, sb, sc, accumulate=False, bf16=Fals
 
 
 TRI_CAUSAL = True   # a causal square attention (the LLM's): the matrix-form products skip the 128 x 128 tiles wholly behind the diagonal and clip their sums to the visible part
-#                     (ullsam_train_matmul_heads `tri`); the row pass writes zeros there without reading.  False: whole matrices (tests / A-B: same bits)
+#                     (ullsam_train_matmul_heads `tri`); the row pass writes zeros there without reading.  False: whole matrices (tests / A-B: same bits).  Not used when
+#                     a query sees only padded keys (left padding): the reference's softmax of such a row is uniform over every single-masked entry, keys behind the diagonal included
 
 
-def _tri(dims) -> bool:
+def _tri(dims, masked_rows=False) -> bool:
     B, H, KVH, hd, Sq, Sk, causal, kw = dims
-    return bool(TRI_CAUSAL and causal == 0 and Sq == Sk)
+    return bool(TRI_CAUSAL and causal == 0 and Sq == Sk and not masked_rows)
+
+
+def _masked_rows(key_mask: Optional[torch.Tensor], causal: int) -> bool:
+    """Does some query see only padded keys?  (Query 0 sees keys 0 .. causal; any query whose visible keys are all padded implies query 0's are.)  Reads the mask back:
+    callers that know it on the host pass it to AttentionFn instead."""
+    return key_mask is not None and causal >= 0 and bool((key_mask[:, :causal + 1] == 0).all(1).any())
 
 
 def _colsum(x2d: torch.Tensor) -> torch.Tensor:
@@ -445,13 +452,17 @@ class AttentionFn(Function):
     ViT's (image_encoder.py:224-240: bias_h [B, H, Sq, Sk/kw] + bias_w [B, H, Sq, kw], the decomposed relative-position terms)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, B, H, KVH, Sq, Sk, causal, key_mask, bias_h, bias_w, kw, bf16=False, fused_out=None):
+    def forward(ctx, q, k, v, B, H, KVH, Sq, Sk, causal, key_mask, bias_h, bias_w, kw, bf16=False, fused_out=None, masked_rows=None):
+        """masked_rows: whether some query sees only padded keys (None: read from key_mask where it matters)."""
         q, k, v = _c(q), _c(k), _c(v)
         ctx.bf16 = bool(bf16)     # matrix form only: the score / probability products as autocast(bfloat16) computes them (bf16 models)
         if bias_h is not None:
             bias_h, bias_w = _c(bias_h), _c(bias_w)
         hd = q.shape[-1] // H
         ctx.dims = (B, H, KVH, hd, Sq, Sk, causal, kw)
+        if masked_rows is None:
+            masked_rows = _masked_rows(key_mask, causal) if (causal == 0 and Sq == Sk) else False
+        ctx.tri = _tri(ctx.dims, masked_rows)
         if Sq * Sk < MATRIX_ATTN_FROM:       # small: one workgroup per query; the backward recomputes P and adds dk / dv by atomics
             out = torch.empty_like(q)
             ctx.save_for_backward(q, k, v, key_mask, bias_h, bias_w)
@@ -466,7 +477,8 @@ class AttentionFn(Function):
             # the caller has the forward value from an inference kernel (the ViT's global blocks: ullsam_vit_attention on the packed qkv); the backward rebuilds P from q / k / v
             ctx.save_for_backward(AttentionFn._scaled(q, 1.0 / math.sqrt(hd)), k, v, key_mask, bias_h, bias_w)
             return _c(fused_out)
-        if (FUSED_CAUSAL_FWD and ctx.inplace and ctx.bf16 and RECOMPUTE_P and causal == 0 and bias_h is None and hd == 128 and Sq == Sk and H % KVH == 0):
+        if (FUSED_CAUSAL_FWD and ctx.inplace and ctx.bf16 and RECOMPUTE_P and causal == 0 and bias_h is None and hd == 128 and Sq == Sk and H % KVH == 0
+                and not masked_rows):   # (the causal kernel skips keys behind the diagonal: a row that sees only padded keys takes the matrix form)
             # The LLM's forward on the inference path's causal kernel (csrc/attention.hip causal128_attn_kernel: bf16 q / k / v, fp32 online softmax, bf16 probabilities and output --
             # autocast's attention; the reference's additive causal + padding masks): no score matrix in the forward at all.  The backward rebuilds P in matrix form from the
             # saved q scale / k / v as before (RECOMPUTE_P), so it needs nothing from this launch.
@@ -483,12 +495,12 @@ class AttentionFn(Function):
             G = H // KVH
             qs = AttentionFn._scaled(q, 1.0 / math.sqrt(hd))
             P = torch.empty((B * H, Sq, Sk), dtype=F32, device=q.device)
-            AttentionFn._scores(qs, k, P, ctx.dims, ctx.bf16)
+            AttentionFn._scores(qs, k, P, ctx.dims, ctx.bf16, ctx.tri)
             _lib.call("ullsam_train_attn_rows", P.data_ptr(), None, ops._p(bias_h), ops._p(bias_w), None, None, ops._p(key_mask), B, H, Sq, Sk, kw,
                       causal, 0, _s())
             out = torch.empty_like(q)
             _mmh(P, v, out, Sq, hd, Sk, B, H, (H * Sq * Sk, Sq * Sk, 1, Sk, 1), (Sk * KVH * hd, hd, G, KVH * hd, 1), (Sq * H * hd, hd, H * hd, 1), bf16=ctx.bf16,
-                 tri=3 if _tri(ctx.dims) else 0)   # out = P v
+                 tri=3 if ctx.tri else 0)   # out = P v
             ctx.save_for_backward(qs, k, v, key_mask if RECOMPUTE_P else P, bias_h, bias_w)
             return out
         # Matrix form (csrc/train.hip attn_rows_kernel) for the decoder's few-token attentions: head-major copies, batched matmuls around one row pass; P is kept for the backward.
@@ -507,11 +519,11 @@ class AttentionFn(Function):
         return oh.permute(0, 2, 1, 3).reshape(B * Sq, H * hd).contiguous()
 
     @staticmethod
-    def _scores(qs, k, P, dims, bf16):
+    def _scores(qs, k, P, dims, bf16, tri):
         """P[(b, h)] = qs_h k_{h // G}^T on the row tensors (qs [B*Sq, H*hd], k [B*Sk, KVH*hd])."""
         B, H, KVH, hd, Sq, Sk, _, _ = dims
         _mmh(qs, k, P, Sq, Sk, hd, B, H, (Sq * H * hd, hd, 1, H * hd, 1), (Sk * KVH * hd, hd, H // KVH, 1, KVH * hd), (H * Sq * Sk, Sq * Sk, Sk, 1), bf16=bf16,
-             tri=1 if _tri(dims) else 0)
+             tri=1 if tri else 0)
 
     @staticmethod
     def _head_major(q, k, v, dims):
@@ -553,7 +565,7 @@ class AttentionFn(Function):
             dbw = torch.empty_like(bias_w) if bias_w is not None else None
             dq, dk, dv = torch.empty_like(q), torch.zeros_like(k), torch.zeros_like(v)
             AttentionFn._launch(q, k, v, dout, None, dq, dk, dv, ctx.dims, key_mask, bias_h, bias_w, dbh, dbw)
-            return (dq, dk, dv) + nones + (dbh, dbw, None, None, None)
+            return (dq, dk, dv) + nones + (dbh, dbw, None, None, None, None)
         if ctx.inplace:
             return AttentionFn._backward_inplace(ctx, dout)
         qs, kh, vh, P, bias_h, bias_w = ctx.saved_tensors
@@ -578,7 +590,7 @@ class AttentionFn(Function):
             red = lambda t: _colsum(t.reshape(B, KVH, G, Sk * hd).permute(2, 0, 1, 3).reshape(G, -1).contiguous()).reshape(B, KVH, Sk, hd)
             dkh, dvh = red(dkh), red(dvh)
         back = lambda t, S_, Hx: t.permute(0, 2, 1, 3).reshape(B * S_, Hx * hd).contiguous()
-        return (back(dqh, Sq, H), back(dkh, Sk, KVH), back(dvh, Sk, KVH)) + nones + (dbh, dbw, None, None, None)
+        return (back(dqh, Sq, H), back(dkh, Sk, KVH), back(dvh, Sk, KVH)) + nones + (dbh, dbw, None, None, None, None)
 
 
 def _attn_backward_inplace(ctx, dout):
@@ -590,13 +602,13 @@ def _attn_backward_inplace(ctx, dout):
     key_mask = None
     if ctx.recompute:
         key_mask, P = P, torch.empty((B * H, Sq, Sk), dtype=F32, device=qs.device)
-        AttentionFn._scores(qs, k, P, ctx.dims, ctx.bf16)
+        AttentionFn._scores(qs, k, P, ctx.dims, ctx.bf16, ctx.tri)
     dbh = torch.empty_like(bias_h) if bias_h is not None else None
     dbw = torch.empty_like(bias_w) if bias_w is not None else None
     sP, sPT = (H * Sq * Sk, Sq * Sk, 1, Sk, 1), (H * Sq * Sk, Sq * Sk, 1, 1, Sk)        # P / dS as [m = q][k = key] and transposed [m = key][k = q]
     rows_q = (Sq * H * hd, hd, 1, H * hd, 1)                                               # dO / qs as the B operand [k = q][n = d] resp. the A operand [m = q][k = d]
     dP = torch.empty_like(P)
-    tri = _tri(ctx.dims)
+    tri = ctx.tri
     _mmh(dout, v, dP, Sq, Sk, hd, B, H, rows_q, (Sk * KVH * hd, hd, G, 1, KVH * hd), (H * Sq * Sk, Sq * Sk, Sk, 1), bf16=ctx.bf16, tri=1 if tri else 0)   # dP = dO v^T
     _lib.call("ullsam_train_attn_rows", P.data_ptr(), dP.data_ptr(), ops._p(bias_h), ops._p(bias_w), ops._p(dbh), ops._p(dbw), ops._p(key_mask), B, H,
               Sq, Sk, kw, causal, 0 if ctx.recompute else 1, _s())                                                          # dP <- dS
@@ -616,7 +628,7 @@ def _attn_backward_inplace(ctx, dout):
         red = lambda t: _colsum(t.reshape(B, KVH, G, Sk * hd).permute(2, 0, 1, 3).reshape(G, -1).contiguous()).reshape(B, KVH, Sk, hd)
         back = lambda t: t.permute(0, 2, 1, 3).reshape(B * Sk, KVH * hd).contiguous()
         dk, dv = back(red(dk)), back(red(dv))
-    return (dq, dk, dv) + (None,) * 7 + (dbh, dbw, None, None, None)
+    return (dq, dk, dv) + (None,) * 7 + (dbh, dbw, None, None, None, None)
 
 
 AttentionFn._backward_inplace = staticmethod(_attn_backward_inplace)
@@ -1166,7 +1178,11 @@ def llm_image_hidden(model, vit_feature_rows: torch.Tensor, input_ids: torch.Ten
     D = vit_embeds.shape[-1]
     ids = input_ids.reshape(-1)
     sel = ids == model.img_context_token_id
-    n_sel = int(sel.sum())
+    lead = None if attention_mask is None else (attention_mask[:, 0] == 0).sum()     # sequences whose key 0 is padded: their first queries see only padded keys
+    if lead is not None and lead.device == sel.device:
+        n_sel, n_lead = torch.stack([sel.sum(), lead]).tolist()                   # (one read-back for both)
+    else:
+        n_sel, n_lead = int(sel.sum()), (0 if lead is None else int(lead))
     if n_sel != vit_embeds.shape[0]:
         raise ValueError(f"{n_sel} <IMG_CONTEXT> tokens for {vit_embeds.shape[0]} image embeddings")
     emb = lm.model.tok_embeddings
@@ -1188,7 +1204,7 @@ def llm_image_hidden(model, vit_feature_rows: torch.Tensor, input_ids: torch.Ten
         q = RoPEFn.apply(q.reshape(B * S, H * hd), pos, cos, sin, H)
         k = RoPEFn.apply(k.reshape(B * S, KVH * hd), pos, cos, sin, KVH)
         v = v.reshape(B * S, KVH * hd)
-        a = AttentionFn.apply(q, k, v, B, H, KVH, S, S, 0, key_mask, None, None, 0, BF16_LINEAR and at.wqkv.weight.dtype == torch.bfloat16)
+        a = AttentionFn.apply(q, k, v, B, H, KVH, S, S, 0, key_mask, None, None, 0, BF16_LINEAR and at.wqkv.weight.dtype == torch.bfloat16, None, n_lead > 0)
         x = AddFn.apply(x, _frozen_linear(a, at.wo.weight, at.wo.bias))
         xn = RMSNormFn.apply(x, layer.ffn_norm.weight, layer.ffn_norm.variance_epsilon)
         hmid = SwiGLUFn.apply(_frozen_linear(xn, ff.w1.weight, None), _frozen_linear(xn, ff.w3.weight, None))
