@@ -27,7 +27,7 @@ extern "C" {
 
 /* Bumped whenever an entry point is added or a signature changes.  The Python binding refuses a library that reports another
    version (a stale libullsam_hip.so would otherwise receive shifted arguments, e.g. a row count where the stream is expected). */
-#define ULLSAM_ABI_VERSION 12
+#define ULLSAM_ABI_VERSION 13
 
 const char* ullsam_last_error_string(void);
 int ullsam_abi_version(void); /* == ULLSAM_ABI_VERSION of the header the library was built from */
@@ -330,6 +330,22 @@ int ullsam_amg_postprocess(const float* low, const int* index, long M, int LH, i
                            void* stream);                      /* sam.py:154-162 + amg.py:156-176, 303-346, 107-135, 251-264 */
 int ullsam_nms_mask(const float* boxes, int N, float iou_threshold, unsigned long long* mask, void* stream); /* torchvision.ops.nms (absent dependency) */
 int ullsam_threshold_u8(const float* in, unsigned char* out, long n, float thr, void* stream); /* masks > mask_threshold */
+/* Connected regions (8-connectivity) of N binary masks at once, for the generator's min_mask_region_area step.
+   rle_to_mask: counts i32 = the records' uncompressed column-major counts, concatenated; offsets i64 [N + 1] into them; masks u8 [N, H, W].
+     status i32 [N] (device) = 1 where a count is negative or a record's counts do not sum to H * W; no store leaves that record's mask
+     (a stream-ordered call cannot know, so the binding reads `status` and raises).
+   label_regions: labels i32 [N, H, W] = the row-major index, within the mask, of the raster-first pixel of the pixel's region, -1 outside
+     the working set (background = 0: the non-zero pixels, 1: the zero pixels).
+   remove_small_regions: mode 0 "holes" sets every region of zeros with size < area_thresh, mode 1 "islands" clears every region of ones
+     with size < area_thresh (all of them small: the largest stays, the raster-first on a tie); area_thresh = ceil of the reference's float;
+     changed u8 [N] = some region was small.  workspace: 16-byte aligned, N * (8 * H * W + 16) bytes, its first N * H * W int32 hold the
+     labels on return; masks_out may be masks_in.  N <= 65535 per call. */
+int ullsam_rle_to_mask(const int* counts, const long* offsets, long N, int H, int W, unsigned char* masks, int* status,
+                       void* stream);                                                         /* amg.py:138-150 */
+int ullsam_label_regions(const unsigned char* masks, long N, int H, int W, int background, int* labels,
+                         void* stream);                                   /* amg.py:276 (cv2.connectedComponentsWithStats(.., 8)) */
+int ullsam_remove_small_regions(const unsigned char* masks_in, unsigned char* masks_out, long N, int H, int W, int area_thresh, int mode,
+                                void* workspace, long workspace_bytes, unsigned char* changed, void* stream);   /* amg.py:267-291 */
 
 /* fp8 (OCP e4m3) ViT path -- BASELINE.json configs[4]; the reference's bf16 encoder linears image_encoder.py:227,171-181 with
    8-bit operands: rows quantised with a per-row scale (optionally behind the block's LayerNorm :166,180), GEMM on the

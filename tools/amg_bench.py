@@ -30,7 +30,8 @@ sam = blob_decoder_init(build_model(vit, "none", torch.bfloat16, "cuda:0"))
 fp8 = os.environ.get("ULLSAM_FP8") == "1"
 sam.image_encoder.fp8_linears = fp8
 gen = SamAutomaticMaskGenerator(sam, points_per_side=side, points_per_batch=int(os.environ.get("AMG_PPB", "64")), pred_iou_thresh=piou, stability_score_thresh=stab,
-                                stability_score_offset=off, box_nms_thresh=nms, output_mode="uncompressed_rle")
+                                stability_score_offset=off, box_nms_thresh=nms, output_mode="uncompressed_rle", min_mask_region_area=int(os.environ.get("AMG_MIN_AREA", "0")),
+                                device_small_regions=os.environ.get("AMG_HOST_REGIONS", "0") != "1")    # AMG_MIN_AREA=100: with the small-region step (AMG_HOST_REGIONS=1: on the host, for A/B)
 gen.pipelined = os.environ.get("AMG_PIPE", "1") != "0"    # AMG_PIPE=0: round 5's per-batch loop (three stream synchronisations per batch), for A/B
 from ullsam_amd.utils.synthetic import microscopy_tile
 img = torch.from_numpy(microscopy_tile(7, size=tile, n_cells=40, r_range=(90.0 * tile / 2048, 260.0 * tile / 2048))[0] * 255).cuda()
@@ -46,5 +47,5 @@ for it in range(iters):
 t_enc, t_all = sorted(encs)[len(encs) // 2] * (iters - 1), sorted(alls)[len(alls) // 2] * (iters - 1)     # medians over the timed tiles (the first tile is a warm-up)
 print(json.dumps({"workload": f"AMG {side}x{side} points on a {tile}^2 tile, SAM ViT-{vit.upper()}, {'fp8 (e4m3) qkv/lin1 + bf16' if fp8 else 'bf16'}, {os.environ.get('AMG_PPB', '64')} prompts/batch, multimask",
                   "seconds_per_tile": round(t_all / (iters - 1), 4), "encoder_seconds": round(t_enc / (iters - 1), 4), "prompts_per_s": round(side * side / (t_all / (iters - 1)), 1),
-                  "masks_kept": len(recs), "thresholds": {"pred_iou": piou, "stability": stab, "stability_offset": off, "box_nms": nms}}))
+                  "masks_kept": len(recs), "min_mask_region_area": gen.min_mask_region_area, "thresholds": {"pred_iou": piou, "stability": stab, "stability_offset": off, "box_nms": nms}}))
 assert len(recs) > 0, "every mask was filtered: the timed tile did no NMS / RLE work"

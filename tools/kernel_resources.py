@@ -32,7 +32,10 @@ HOT_BF16 = [r"gemm_ring8_kernelILi\d+ELi\d+ELi\d+ELb0E", r"gemm256_kernelIDF16bL
 # epilogue cannot take (unaligned q / k / v): not on the bench path, not in this list)
 HOT_AMG = [r"i2t_block_kernel", r"kv_proj_kernel", r"up1_ln_gelu_kernel", r"up2_hyper_kernel", r"tok2img_partial_mfma_kernel", r"tok2img_merge_kernel", r"dec_tok_attn_kernel", r"dec_tok_mlp_kernel",
            r"dec_heads_kernel", r"amg_postprocess_kernel", r"rle_emit_kernel"]
-HOT_BF16 = HOT_BF16 + HOT_AMG
+# the generator's min_mask_region_area step (csrc/regions.hip): labelling, areas, removal, inverse RLE
+HOT_REGIONS = [r"label_tile_kernel", r"label_merge_kernel", r"label_flatten_kernel", r"region_area_kernel", r"region_decide_kernel", r"region_apply_kernel",
+               r"rle_expand_kernel"]
+HOT_BF16 = HOT_BF16 + HOT_AMG + HOT_REGIONS
 HOT = HOT_BF16
 # round 6: the persistent ring kernel in its default schedule (SCHED 2, no stamps, no ablation): no spilled VECTOR register and no scratch.  Its tile loop keeps more scalars than the 102 SGPRs hold
 # (tile coordinates, two buffer descriptors, the kernel arguments the epilogue reads): hipcc parks the overflow in lanes of a VGPR (v_writelane / v_readlane, outside the K loop) -- counted as

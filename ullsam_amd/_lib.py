@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ULLSAM_HIP_LIB") or os.path.join(_HERE, "lib", "libullsam_hip.so")  # env: A/B a side build (developer switch)
 
-ABI_VERSION = 12  # == ULLSAM_ABI_VERSION in include/ullsam_hip.h (tests/test_host_cpu.py checks the three agree)
+ABI_VERSION = 13  # == ULLSAM_ABI_VERSION in include/ullsam_hip.h (tests/test_host_cpu.py checks the three agree)
 
 _lib = None
 
@@ -88,6 +88,9 @@ SIGNATURES = {
     "ullsam_amg_postprocess": [vp, vp, i64] + [i32] * 11 + [f32, f32, vp, vp, vp, vp, vp, vp],
     "ullsam_nms_mask": [vp, i32, f32, vp, vp],
     "ullsam_threshold_u8": [vp, vp, i64, f32, vp],
+    "ullsam_rle_to_mask": [vp, vp, i64, i32, i32, vp, vp, vp],
+    "ullsam_label_regions": [vp, i64, i32, i32, i32, vp, vp],
+    "ullsam_remove_small_regions": [vp, vp, i64, i32, i32, i32, i32, vp, i64, vp, vp],
     "ullsam_rows_fp8": [vp, i32, i64, vp, i64, vp, vp, vp, i64, i32, f32, vp],
     "ullsam_gemm_fp8": [vp, i64, vp, vp, i64, vp, vp, i64, i32, vp, vp, i64, i32, i32, i32, i32, vp],
 }

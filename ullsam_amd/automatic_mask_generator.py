@@ -9,7 +9,10 @@ small crops).  Helper parity is pinned (tests/golden/amg.npz); driver parity is 
 flow over the oracle (tests/test_amg_gpu.py).
 
 Deviations, stated: images are resized with the bilinear kernel (align_corners=False, no antialias) instead of PIL's antialiased
-uint8 resize; `min_mask_region_area` post-processing labels regions with scipy instead of OpenCV (utils.amg.remove_small_regions);
+uint8 resize; `min_mask_region_area` post-processing labels regions on the GPU (csrc/regions.hip: batched 8-connected union-find,
+utils.amg.remove_small_regions_batched) instead of OpenCV on the host -- only region membership and integer sizes are used, so the
+records are the same bits; `device_small_regions=False` runs the host form of the step (utils.amg.remove_small_regions, scipy as the
+labeller), which is the definition the device path is tested against, and is what a model on the CPU gets;
 the predicted-IoU filter is applied before
 the masks are upsampled (it depends only on the IoU head, so the surviving set is identical, and the 3x1024^2-per-prompt logits of
 rejected masks are never materialised).  With `fused_postprocess=True` (default) the upsample, stability score, mask->box and RLE
@@ -33,7 +36,8 @@ class SamAutomaticMaskGenerator:
                  stability_score_thresh: float = 0.95, stability_score_offset: float = 1.0, box_nms_thresh: float = 0.7,
                  crop_n_layers: int = 0, crop_nms_thresh: float = 0.7, crop_overlap_ratio: float = 512 / 1500,
                  crop_n_points_downscale_factor: int = 1, point_grids: Optional[List[np.ndarray]] = None,
-                 min_mask_region_area: int = 0, output_mode: str = "binary_mask", fused_postprocess: bool = True) -> None:
+                 min_mask_region_area: int = 0, output_mode: str = "binary_mask", fused_postprocess: bool = True,
+                 device_small_regions: bool = True) -> None:
         assert (points_per_side is None) != (point_grids is None), "Exactly one of points_per_side or point_grid must be provided."
         self.point_grids = (A.build_all_layer_point_grids(points_per_side, crop_n_layers, crop_n_points_downscale_factor)
                             if points_per_side is not None else point_grids)
@@ -50,6 +54,7 @@ class SamAutomaticMaskGenerator:
         self.crop_overlap_ratio = crop_overlap_ratio
         self.output_mode = output_mode
         self.fused_postprocess = fused_postprocess
+        self.device_small_regions = device_small_regions
 
     # -- image side --------------------------------------------------------------------------------------------------
     def _encode(self, crop: torch.Tensor):
@@ -230,6 +235,8 @@ class SamAutomaticMaskGenerator:
         if len(data["rles"]) == 0:
             return data
         dev = data["boxes"].device
+        if self.device_small_regions and dev.type == "cuda":
+            return self._postprocess_small_regions_device(data, min_area, nms_thresh)
         new_masks, scores = [], []
         for rle in data["rles"]:
             mask = A.rle_to_mask(rle)
@@ -246,6 +253,62 @@ class SamAutomaticMaskGenerator:
             if scores[i] == 0.0:
                 data["rles"][i] = A.mask_to_rle_pytorch(masks[i:i + 1])[0]
                 data["boxes"][i] = boxes[i]
+        data.filter(keep)
+        return data
+
+    def _postprocess_small_regions_device(self, data: A.MaskData, min_area: int, nms_thresh: float, timings: Optional[dict] = None) -> A.MaskData:
+        """The same step with the masks never leaving the GPU.  Per chunk of ops.region_chunk(H, W) records (8 at 2048^2, so the labelling
+        workspace does not grow with the number of records): expand the RLEs, fill small holes, remove small islands of the result, take the
+        boxes; ONE read-back per chunk (changed flags and RLE status).  The cleaned masks of the changed records stay on the device (1 byte per
+        pixel; the host form keeps ALL masks there) until the box NMS over all records -- scores 1.0 unchanged / 0.0 changed, as the host form
+        -- has chosen which to keep; only changed, kept masks are encoded again.  `timings`: per-phase seconds, synchronising (tools only)."""
+        import time
+        rles = data["rles"]
+        dev = data["boxes"].device
+        n = len(rles)
+        h, w = (int(v) for v in rles[0]["size"])
+        step = ops.region_chunk(h, w)
+        clock = None
+        if timings is not None:
+            def clock(key, t0):
+                torch.cuda.synchronize()
+                timings[key] = timings.get(key, 0.0) + time.perf_counter() - t0
+                return time.perf_counter()
+        boxes_all, changed_all, saved = [], [], {}
+        for s in range(0, n, step):
+            t0 = time.perf_counter()
+            masks, status = A._rle_expand(rles[s:s + step], dev)
+            if clock: t0 = clock("expand", t0)
+            masks, ch_h = A.remove_small_regions_batched(masks, min_area, "holes", inplace=True)
+            if clock: t0 = clock("label_holes", t0)
+            masks, ch_i = A.remove_small_regions_batched(masks, min_area, "islands", inplace=True)
+            if clock: t0 = clock("label_islands", t0)
+            boxes_all.append(A.batched_mask_to_box(masks))
+            flags = torch.stack([(ch_h | ch_i).to(torch.uint8), (status != 0).to(torch.uint8)]).cpu().numpy()
+            if flags[1].any():
+                raise A._lib.UllsamError(f"postprocess_small_regions: the counts of record {s + int(np.nonzero(flags[1])[0][0])} are negative or do not sum to H * W")
+            changed_all.append(flags[0].astype(bool))
+            idx = np.nonzero(flags[0])[0]
+            if len(idx) == masks.shape[0]:
+                kept = masks
+            elif len(idx):
+                kept = masks[torch.from_numpy(idx).to(dev)]
+            for j, i in enumerate(idx):
+                saved[s + int(i)] = kept[j]
+            if clock: t0 = clock("boxes_readback", t0)
+        t0 = time.perf_counter()
+        boxes = torch.cat(boxes_all, 0)
+        changed = np.concatenate(changed_all)
+        scores = torch.as_tensor([0.0 if c else 1.0 for c in changed], device=dev)
+        keep = A.batched_nms(boxes.float(), scores, torch.zeros_like(boxes[:, 0]), nms_thresh)
+        if clock: t0 = clock("nms", t0)
+        redo = [i for i in keep.tolist() if changed[i]]
+        for a in range(0, len(redo), step):
+            part = redo[a:a + step]
+            for i, rle in zip(part, A.mask_to_rle_pytorch(torch.stack([saved[i] for i in part]))):
+                data["rles"][i] = rle
+                data["boxes"][i] = boxes[i]
+        if clock: t0 = clock("reencode", t0)
         data.filter(keep)
         return data
 

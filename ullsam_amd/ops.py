@@ -625,3 +625,74 @@ def mask_iou(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     _lib.call("ullsam_mask_iou_counts", a.data_ptr(), b.data_ptr(), counts.data_ptr(), N, per, _stream())
     c = counts.double()
     return (c[:, 0] + 1e-7) / (c[:, 1] + 1e-7)
+
+
+# ---- connected regions of binary masks (csrc/regions.hip) ---------------------------------------------------------------------
+REGION_CHUNK_PIXELS = 1 << 25    # pixels labelled per call: 8 masks of 2048^2
+REGION_MODES = {"holes": 0, "islands": 1}
+
+
+def region_chunk(h: int, w: int) -> int:
+    """How many [h, w] masks one labelling call takes, so that the workspace does not grow with the number of records."""
+    return max(1, min(REGION_CHUNK_PIXELS // max(h * w, 1), 4096))
+
+
+def region_workspace(n: int, h: int, w: int, device) -> torch.Tensor:
+    """Caller-owned scratch of `remove_small_regions`, one buffer per device and stream, grown on demand: n * (8 * h * w + 16) bytes
+    = int32 labels + int32 areas (16 + 16 MiB per 2048^2 mask) + 16 bytes per mask.  With n <= region_chunk(h, w) that is at most
+    8 * max(h * w, 2^25) bytes + 64 KiB (256 MiB up to 2048^2 frames), whatever the number of records."""
+    need = n * (8 * h * w + 16)
+    key = ("regions", str(device), torch.cuda.current_stream().cuda_stream)
+    ws = _WS.get(key)
+    if ws is None or ws.numel() < need:
+        _WS.pop(key, None)
+        ws = _WS[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
+def rle_to_mask(counts: torch.Tensor, offsets: torch.Tensor, h: int, w: int):
+    """Uncompressed column-major RLEs (all counts concatenated, int32; offsets int64 [N + 1]) -> (masks uint8 [N, h, w], status int32 [N]).
+    status is 1 for a record whose counts are negative or do not sum to h * w (its mask then holds the in-range part): the caller reads it."""
+    _chk(counts, "counts", torch.int32); _chk(offsets, "offsets", torch.int64)
+    n = offsets.numel() - 1
+    assert n >= 0 and h > 0 and w > 0
+    masks = torch.empty((n, h, w), dtype=torch.uint8, device=counts.device)
+    status = torch.empty((n,), dtype=torch.int32, device=counts.device)
+    _lib.call("ullsam_rle_to_mask", counts.data_ptr(), offsets.data_ptr(), n, h, w, masks.data_ptr(), status.data_ptr(), _stream())
+    return masks, status
+
+
+def label_regions(masks: torch.Tensor, background: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """masks uint8 [N, H, W] -> int32 labels [N, H, W]: the index of the raster-first pixel of the pixel's 8-connected region, -1 outside
+    the working set (the non-zero pixels, or the zero pixels with background=True).  N <= 65535 (utils.amg.label_regions chunks)."""
+    _chk(masks, "masks", torch.uint8)
+    n, h, w = masks.shape
+    if out is None:
+        out = torch.empty((n, h, w), dtype=torch.int32, device=masks.device)
+    else:
+        _chk(out, "out", torch.int32)
+        assert out.shape == masks.shape
+    _lib.call("ullsam_label_regions", masks.data_ptr(), n, h, w, int(bool(background)), out.data_ptr(), _stream())
+    return out
+
+
+def remove_small_regions(masks: torch.Tensor, area_thresh: int, mode: str, out: Optional[torch.Tensor] = None,
+                         changed: Optional[torch.Tensor] = None):
+    """One call of the region kernels over masks uint8 [N, H, W], N <= region_chunk(H, W) -> (masks uint8 [N, H, W], changed uint8 [N],
+    labels int32 [N, H, W]: a view of the workspace, valid until the next call on this stream).  `out` may be `masks`."""
+    _chk(masks, "masks", torch.uint8)
+    n, h, w = masks.shape
+    if out is None:
+        out = torch.empty_like(masks)
+    else:
+        _chk(out, "out", torch.uint8)
+        assert out.shape == masks.shape
+    if changed is None:
+        changed = torch.empty((n,), dtype=torch.uint8, device=masks.device)
+    else:
+        _chk(changed, "changed", torch.uint8)
+        assert changed.numel() == n
+    ws = region_workspace(n, h, w, masks.device)
+    _lib.call("ullsam_remove_small_regions", masks.data_ptr(), out.data_ptr(), n, h, w, int(area_thresh), REGION_MODES[mode], ws.data_ptr(),
+              ws.numel(), changed.data_ptr(), _stream())
+    return out, changed, ws[:n * h * w * 4].view(torch.int32).view(n, h, w)

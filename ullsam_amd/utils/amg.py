@@ -422,3 +422,73 @@ def batched_nms(boxes: torch.Tensor, scores: torch.Tensor, idxs: torch.Tensor, i
     max_coord = boxes.max()
     offsets = idxs.to(boxes) * (max_coord + 1)
     return box_nms(boxes + offsets[:, None], scores, iou_threshold)
+
+
+# ---- connected regions on the device (csrc/regions.hip) ---------------------------------------------------------------------
+def _rle_expand(rles: Sequence[Dict[str, Any]], device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """RLE dicts of ONE frame size -> (masks uint8 [N, H, W], status int32 [N]) on `device`, nothing read back."""
+    from .. import ops
+    h, w = (int(v) for v in rles[0]["size"])
+    cs = []
+    for r in rles:
+        if [int(v) for v in r["size"]] != [h, w]:
+            raise _lib.UllsamError(f"rle_to_mask_device: records of different sizes ({r['size']} vs {[h, w]})")
+        cs.append(np.clip(np.asarray(r["counts"], dtype=np.int64).reshape(-1), -1, 2 ** 31 - 1))     # (out-of-range counts stay wrong)
+    offs = np.concatenate([[0], np.cumsum([len(c) for c in cs])]).astype(np.int64)
+    flat = np.concatenate(cs).astype(np.int32) if offs[-1] else np.zeros((1,), np.int32)
+    return ops.rle_to_mask(torch.from_numpy(flat).to(device), torch.from_numpy(offs).to(device), h, w)
+
+
+def rle_to_mask_device(rles: Sequence[Dict[str, Any]], device) -> torch.Tensor:
+    """`rle_to_mask` (amg.py:138-150) of N records of one frame size, on the device -> uint8 [N, H, W].  Counts that are negative or do
+    not sum to H * W raise UllsamError."""
+    if len(rles) == 0:
+        return torch.zeros((0, 0, 0), dtype=torch.uint8, device=device)
+    masks, status = _rle_expand(rles, device)
+    bad = np.nonzero(status.cpu().numpy())[0]
+    if len(bad):
+        raise _lib.UllsamError(f"rle_to_mask_device: the counts of record {int(bad[0])} ({len(bad)} in all) are negative or do not sum to H * W")
+    return masks
+
+
+def label_regions(masks: torch.Tensor, background: bool = False) -> torch.Tensor:
+    """8-connected regions of the set pixels (background=True: of the zero pixels) of masks [N, H, W] (or [H, W]) -> int32 labels of the
+    same shape: every pixel of a region carries the row-major index, within its mask, of the region's raster-first pixel; -1 elsewhere.
+    The regions are those of scipy.ndimage.label(structure=ones((3, 3))) / cv2.connectedComponents(.., 8); the labels depend on the mask only."""
+    from .. import ops
+    m = _as_u8(masks)
+    m3 = m.reshape((-1,) + tuple(m.shape[-2:]))
+    n, h, w = m3.shape
+    out = torch.empty((n, h, w), dtype=torch.int32, device=m.device)
+    if n and h and w:
+        step = ops.region_chunk(h, w)
+        for s in range(0, n, step):
+            ops.label_regions(m3[s:s + step], background, out=out[s:s + step])
+    return out.reshape(masks.shape)
+
+
+def area_thresh_int(area_thresh: float) -> int:
+    """Region sizes are integers, so `size < area_thresh` is `size < ceil(area_thresh)`."""
+    return int(min(max(math.ceil(float(area_thresh)), 0), 2 ** 31 - 1))
+
+
+def remove_small_regions_batched(masks: torch.Tensor, area_thresh: float, mode: str, return_labels: bool = False, inplace: bool = False):
+    """`remove_small_regions` of every mask of [N, H, W] (bool or uint8, on the GPU) -> (masks of the same dtype, changed bool [N]), the same
+    bits as the host function mask by mask.  Masks are processed in chunks of ops.region_chunk(H, W), so the workspace (ops.region_workspace)
+    is bounded whatever N is.  Nothing is read back.  return_labels=True adds the int32 labels the regions were taken from (N * H * W * 4 bytes)."""
+    from .. import ops
+    assert mode in ("holes", "islands")
+    src = _as_u8(masks)
+    n, h, w = src.shape
+    thr = area_thresh_int(area_thresh)
+    out = src if (inplace and src.data_ptr() == masks.data_ptr()) else torch.empty_like(src)
+    changed = torch.zeros((n,), dtype=torch.uint8, device=src.device)
+    labels = torch.empty((n, h, w), dtype=torch.int32, device=src.device) if return_labels else None
+    if n and h and w:
+        step = ops.region_chunk(h, w)
+        for s in range(0, n, step):
+            _, _, lab = ops.remove_small_regions(src[s:s + step], thr, mode, out=out[s:s + step], changed=changed[s:s + step])
+            if return_labels:
+                labels[s:s + step].copy_(lab)
+    res = out.view(torch.bool) if masks.dtype == torch.bool else out
+    return (res, changed.bool(), labels) if return_labels else (res, changed.bool())
