@@ -27,7 +27,7 @@ extern "C" {
 
 /* Bumped whenever an entry point is added or a signature changes.  The Python binding refuses a library that reports another
    version (a stale libullsam_hip.so would otherwise receive shifted arguments, e.g. a row count where the stream is expected). */
-#define ULLSAM_ABI_VERSION 13
+#define ULLSAM_ABI_VERSION 14
 
 const char* ullsam_last_error_string(void);
 int ullsam_abi_version(void); /* == ULLSAM_ABI_VERSION of the header the library was built from */
@@ -354,6 +354,24 @@ int ullsam_rows_fp8(const void* in, int in_dtype, long in_stride, void* out_e4m3
                     const float* ln_b, long rows, int D, float eps, void* stream);
 int ullsam_gemm_fp8(const void* A8, long lda, const float* a_scale, const void* W8, long ldw, const float* w_scale, void* C, long ldc,
                     int out_f32, const float* bias, const float* residual, long ldr, int act, int M, int N, int K, void* stream);
+
+/* Weight-only fp8 (OCP e4m3) for the LLM's decode steps (InternLM2ForCausalLM.fp8_decode): the layers' wqkv / wo / packed w13 / w2 and the
+   LM head `output` (modeling_internlm2.py:261-264, 341-426, 1081-1082) stored as e4m3 bytes [N, K] with one fp32 scale per output channel,
+   streamed by the decode-step kernels in place of the bf16 rows; activations and accumulation as in the bf16 forms.
+   ullsam_rows_fp8_pow2: per row, scale = the smallest power of two with amax / scale <= 448 (1 for a zero row), saturating round to nearest
+   even.  q * scale of a bf16 weight is exact in bf16, so the kernels below compute what the bf16 kernels compute on those dequantised weights.
+   ullsam_gemm_w8: C = act((a @ W8^T) * w_scale + bias) (+ residual) for M <= 8 rows, K % 512 == 0; a = bf16 `A` [M, K] (norm_w NULL) or
+   bf16(RMSNorm(x) * norm_w) of fp32 x as ullsam_gemm_rmsnorm (M <= 4, K <= 4096, K % 2048 == 0); act 0..3 as ullsam_gemm.
+   ullsam_decode_qkv_rope_w8: ullsam_decode_qkv_rope on e4m3 wqkv.  Shapes the decode-step kernels do not take are an error, not a fallback. */
+int ullsam_rows_fp8_pow2(const void* in, int in_dtype, long in_stride, void* out_e4m3, long out_stride, float* row_scale, long rows, int D,
+                         void* stream);
+int ullsam_gemm_w8(const void* A, const float* x, long ldx, const float* norm_w, float eps, const void* W8, long ldw, const float* w_scale,
+                   void* C, long ldc, int out_f32, const float* bias, const float* residual, long ldr, int act, int M, int N, int K,
+                   void* stream);
+int ullsam_decode_qkv_rope_w8(const void* a, const float* x, long ldx, const float* norm_w, float eps, const void* W8, long ldw,
+                              const float* w_scale, const float* bias, int B, int K, int KVH, int G, const int* pos, const float* cos_tab,
+                              const float* sin_tab, int tab_rows, void* q_out, void* k_cache, void* v_cache, int cap, int cache_pos0,
+                              void* stream);
 
 #ifdef __cplusplus
 }

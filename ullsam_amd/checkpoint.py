@@ -66,14 +66,21 @@ def load_llm_safetensors(model: torch.nn.Module, path_or_dir: str, prefix: str =
     return _report(model, sd)
 
 
-def prepack(model: torch.nn.Module, fp8_vit: bool = False) -> int:
+def prepack(model: torch.nn.Module, fp8_vit: bool = False, fp8_decode: bool = False) -> int:
     """Build the derived weight layouts once, right after loading, instead of inside the first forward ("into the
     build's weight layout ... pre-packing for MFMA tiles"): the compute-dtype copies and fp32 biases of every Linear, the interleaved
-    [gate | up] rows of every InternLM2MLP (SwiGLU epilogue), and -- with fp8_vit -- the e4m3 bytes + per-channel scales of the ViT's qkv / lin1.
+    [gate | up] rows of every InternLM2MLP (SwiGLU epilogue), and -- with fp8_vit -- the e4m3 bytes + per-channel scales of the ViT's qkv / lin1;
+    with fp8_decode the e4m3 copies InternLM2ForCausalLM.fp8_decode streams in its decode steps (every layer's wqkv / wo / packed w13 / w2 and the LM head
+    of a bf16 model on the GPU; about half the LLM's bf16 bytes in extra memory).
     The packs live in each module's PackCache keyed by the parameter version, so an optimizer step or load_state_dict invalidates them.
     Returns the number of packs built.  Needs the model on the GPU (the fp8 quantiser is a HIP kernel)."""
     from .modeling.common import Linear
+    from .modeling.modeling_internlm2 import InternLM2DecoderLayer, InternLM2ForCausalLM
     n = 0
+
+    def w8d_ok(lin):
+        return lin.weight.is_cuda and lin.weight.dtype == torch.bfloat16 and lin.weight.shape[1] % 512 == 0
+
     for name, m in model.named_modules():
         if isinstance(m, Linear):
             m.w(m.weight.dtype)
@@ -84,5 +91,14 @@ def prepack(model: torch.nn.Module, fp8_vit: bool = False) -> int:
                 n += 1
         if hasattr(m, "w13") and hasattr(m, "w1"):
             m.w13(m.w1.weight.dtype)
+            n += 1
+        if fp8_decode and isinstance(m, InternLM2DecoderLayer) and w8d_ok(m.attention.wqkv):
+            m.attention.wqkv.w8d(); m.attention.wo.w8d(); m.feed_forward.w13_w8d(torch.bfloat16)
+            n += 3
+            if w8d_ok(m.feed_forward.w2):
+                m.feed_forward.w2.w8d()
+                n += 1
+        if fp8_decode and isinstance(m, InternLM2ForCausalLM) and w8d_ok(m.output):
+            m.output.w8d()
             n += 1
     return n

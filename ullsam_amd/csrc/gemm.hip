@@ -643,6 +643,7 @@ __global__ __launch_bounds__(NT) void gemm256_tail_reduce_kernel(GemmArgs p) {
 
 // Helpers of the direct (accumulator -> memory) epilogues of the ring kernel.
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 __device__ __forceinline__ void gstore16(void* ptr, u32x4 v) {   // exactly one global_store_dwordx4 (the counted vmcnt waits rely on it)
     *reinterpret_cast<u32x4*>(ptr) = v;
@@ -1534,6 +1535,32 @@ __device__ __forceinline__ uint4 load_w16(const bf16* ptr) {
     return *reinterpret_cast<const uint4*>(ptr);
 #endif
 }
+// The e4m3-weight forms (template parameter W8) of the three kernels below: the weight matrix holds OCP e4m3 bytes [N, K] with one fp32
+// power-of-two scale per row (csrc/norm.hip rows_fp8_pow2_kernel).  A lane keeps the k mapping of the bf16 forms -- its 8 weights of a
+// 512-element step are now 8 bytes, not 16 -- so a register buffer holds half the dwords; the bytes are widened to packed bf16 (exact: e4m3 has
+// 3 mantissa bits) only when the step is multiplied, after the next loads have been issued, and go through the same dot2c sequence in the
+// same order.  The row's scale multiplies the finished fp32 sum once, in the epilogue: a power of two commutes with every fp32 rounding
+// of the sum, so the result is the bf16 kernel's on the dequantised weights.
+template <bool W8> struct SkinnyW { using elem = bf16; using vec = uint4; };
+template <> struct SkinnyW<true> { using elem = unsigned char; using vec = uint2; };
+__device__ __forceinline__ uint2 load_w16(const unsigned char* ptr) {   // 8 e4m3 weights
+#if ULLSAM_SKINNY_NT
+    const u32x2 v = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(ptr));
+    return make_uint2(v[0], v[1]);
+#else
+    return *reinterpret_cast<const uint2*>(ptr);
+#endif
+}
+__device__ __forceinline__ uint4 widen_w(const uint4 w) { return w; }
+__device__ __forceinline__ uint4 widen_w(const uint2 w) {   // bytes 0..7 -> bf16 pairs (0,1) (2,3) (4,5) (6,7): v_cvt_scalef32_pk_bf16_fp8, scale 1
+    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+    uint4 o;
+    o.x = __builtin_bit_cast(unsigned int, (bf16x2_t)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w.x, 1.0f, false));
+    o.y = __builtin_bit_cast(unsigned int, (bf16x2_t)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w.x, 1.0f, true));
+    o.z = __builtin_bit_cast(unsigned int, (bf16x2_t)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w.y, 1.0f, false));
+    o.w = __builtin_bit_cast(unsigned int, (bf16x2_t)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w.y, 1.0f, true));
+    return o;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Skinny GEMM for the decode step (M <= 8 rows, bf16): every weight byte is needed once and nothing is reused across rows of W, so
@@ -1642,13 +1669,15 @@ __device__ __forceinline__ void stage_rmsnorm_finish(const NormRows<MM>& n, char
     __syncthreads();
 }
 
-template <int MM, bool NORM = false>
+template <int MM, bool NORM = false, bool W8 = false>
 __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmArgs p) {
+    using WT = typename SkinnyW<W8>::elem;
+    using WV = typename SkinnyW<W8>::vec;
     extern __shared__ __attribute__((aligned(16))) char smem[];  // A as bf16 [MM][K]
     const int tid = threadIdx.x, lane = tid & 63;
     const int K = p.K, KC = K >> 3;                 // 16-byte chunks per row
     const bf16* A = reinterpret_cast<const bf16*>(p.A);
-    const bf16* W = reinterpret_cast<const bf16*>(p.W);
+    const WT* W = reinterpret_cast<const WT*>(p.W);
     const long wid = (long)blockIdx.x * 4 + (tid >> 6);
     long rows[4];
     if (p.act == 3) {  // packed w13: 128-row blocks [64 gate | 64 up]; this wave: gate rows g, g+1 and their up rows
@@ -1658,12 +1687,12 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmArgs p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) rows[r] = wid * 4 + r;
     }
-    const bf16* wr[4];
+    const WT* wr[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) wr[r] = W + (size_t)min(rows[r], (long)p.N - 1) * p.ldw + lane * 8;
     // the first two steps of the weight stream are requested before the activations are staged: the stream does not depend on them
-    uint4 b0[4], b1[4], b2[4];
-    auto fill = [&](uint4 (&b)[4], const int k) {
+    WV b0[4], b1[4], b2[4];
+    auto fill = [&](WV (&b)[4], const int k) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) b[r] = load_w16(wr[r] + k);
     };
@@ -1699,18 +1728,20 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmArgs p) {
     // Three register buffers of four 1 KiB row segments rotate: two steps of loads are in flight while the third is multiplied.  The dot
     // products are opaque asm to the scheduler, which would otherwise serialise load -> wait -> 16 dots with one buffer; the
     // sched_barriers pin "issue the loads, then compute".
-    auto step = [&](const uint4 (&b)[4], const int k) {
+    auto step = [&](const WV (&b)[4], const int k) {
         uint4 av[MM];
 #pragma unroll
         for (int m = 0; m < MM; ++m) av[m] = *reinterpret_cast<const uint4*>(xa + ((size_t)m * KC + (k >> 3)) * 16);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
+        for (int r = 0; r < 4; ++r) {
+            const uint4 w = widen_w(b[r]);
 #pragma unroll
             for (int m = 0; m < MM; ++m) {
-                dot2c(acc[r * MM + m], b[r].x, av[m].x); dot2c(acc[r * MM + m], b[r].y, av[m].y);
-                dot2c(acc[r * MM + m], b[r].z, av[m].z); dot2c(acc[r * MM + m], b[r].w, av[m].w);
+                dot2c(acc[r * MM + m], w.x, av[m].x); dot2c(acc[r * MM + m], w.y, av[m].y);
+                dot2c(acc[r * MM + m], w.z, av[m].z); dot2c(acc[r * MM + m], w.w, av[m].w);
             }
+        }
         __builtin_amdgcn_sched_barrier(0);
     };
     for (int k0 = 0; k0 < K; k0 += 1536) {
@@ -1731,14 +1762,18 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmArgs p) {
         const float upv = __shfl_xor(tot, 32, 64);       // rows 2, 3 (the up rows) live 32 lanes above rows 0, 1
         if ((lane & ((1 << SH) - 1)) || lane >= 32 || m >= p.M) return;
         const long oc = (rows[0] >> 7) * 64 + (rows[0] & 63) + r;  // output column of gate row rows[r]
-        const float o = silu_f(tot) * upv;
+        float gate = tot, up = upv;
+        if constexpr (W8) { gate *= p.col_scale[rows[0] + r]; up *= p.col_scale[rows[0] + 64 + r]; }   // gate and up rows carry their own scales
+        const float o = silu_f(gate) * up;
         if (p.out_f32) reinterpret_cast<float*>(p.C)[(size_t)m * p.ldc + oc] = o;
         else reinterpret_cast<bf16*>(p.C)[(size_t)m * p.ldc + oc] = (bf16)o;
         return;
     }
     const long n = rows[0] + r;
     if ((lane & ((1 << SH) - 1)) || n >= p.N || m >= p.M) return;
-    float v = tot + (p.bias ? p.bias[n] : 0.f);
+    float v = tot;
+    if constexpr (W8) v *= p.col_scale[n];
+    v += p.bias ? p.bias[n] : 0.f;
     if (p.act == 1) v = gelu_erf(v);
     else if (p.act == 2) v = fmaxf(v, 0.f);
     if (p.residual) v += p.residual[(size_t)(p.res_row_mod > 0 ? m % p.res_row_mod : m) * p.ldr + n];
@@ -1751,14 +1786,16 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmArgs p) {
 // partly filled round of workgroups, and a wave's stream of 1 KiB steps runs through the unit boundaries (the next unit's first steps are
 // already in flight while the finished unit is reduced and stored).  W waves per workgroup, chosen by the launcher so that
 // units = CUs x W x trips comes out even (w13: 7168 units = 256 x 7 x 4).
-template <bool NORM>
+template <bool NORM, bool W8 = false>
 __global__ __launch_bounds__(512) void gemm_skinny_persist_kernel(GemmArgs p, int units) {
+    using WT = typename SkinnyW<W8>::elem;
+    using WV = typename SkinnyW<W8>::vec;
     constexpr int MM = 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];  // A as bf16 [4][K]
     __shared__ float nred[16];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, W = blockDim.x >> 6;
     const int K = p.K, KC = K >> 3, KS = K >> 9;
-    const bf16* Wl = reinterpret_cast<const bf16*>(p.W) + lane * 8;
+    const WT* Wl = reinterpret_cast<const WT*>(p.W) + lane * 8;
     const int stride = gridDim.x * W, u0 = blockIdx.x * W + wv;
     const int n_mine = u0 < units ? (units - 1 - u0) / stride + 1 : 0;
     const int total = n_mine * KS;
@@ -1767,7 +1804,7 @@ __global__ __launch_bounds__(512) void gemm_skinny_persist_kernel(GemmArgs p, in
     // fill cursor: (unit, k) of the next step to request.  Past the end the loads go to the matrix' first row (cache hits): no branch, so
     // the compiler's load counting stays exact and a wait for one buffer never includes the next
     int fu = u0, fk = 0, fleft = total;
-    auto fill_next = [&](uint4 (&b)[4]) {
+    auto fill_next = [&](WV (&b)[4]) {
         const bool on = fleft > 0;
         const long r0 = on ? row0_of(fu) : 0;
 #pragma unroll
@@ -1779,7 +1816,7 @@ __global__ __launch_bounds__(512) void gemm_skinny_persist_kernel(GemmArgs p, in
         if (fk >= K) { fk = 0; fu += stride; }
         --fleft;
     };
-    uint4 b0[4], b1[4], b2[4];
+    WV b0[4], b1[4], b2[4];
     if constexpr (NORM) {
         NormRows<4> nrows;
         stage_rmsnorm_load<4>(nrows, p, tid < 256);
@@ -1814,14 +1851,18 @@ __global__ __launch_bounds__(512) void gemm_skinny_persist_kernel(GemmArgs p, in
             const float upv = __shfl_xor(tot, 32, 64);
             if (!(lane & 3) && lane < 32 && m < p.M) {
                 const long oc = (r0 >> 7) * 64 + (r0 & 63) + r;
-                const float o = silu_f(tot) * upv;
+                float gate = tot, up = upv;
+                if constexpr (W8) { gate *= p.col_scale[r0 + r]; up *= p.col_scale[r0 + 64 + r]; }
+                const float o = silu_f(gate) * up;
                 if (p.out_f32) reinterpret_cast<float*>(p.C)[(size_t)m * p.ldc + oc] = o;
                 else reinterpret_cast<bf16*>(p.C)[(size_t)m * p.ldc + oc] = (bf16)o;
             }
         } else {
             const long n = r0 + r;
             if (!(lane & 3) && n < p.N && m < p.M) {
-                float v = tot + (p.bias ? p.bias[n] : 0.f);
+                float v = tot;
+                if constexpr (W8) v *= p.col_scale[n];
+                v += p.bias ? p.bias[n] : 0.f;
                 if (p.act == 1) v = gelu_erf(v);
                 else if (p.act == 2) v = fmaxf(v, 0.f);
                 if (p.residual) v += p.residual[(size_t)(p.res_row_mod > 0 ? m % p.res_row_mod : m) * p.ldr + n];
@@ -1832,18 +1873,20 @@ __global__ __launch_bounds__(512) void gemm_skinny_persist_kernel(GemmArgs p, in
 #pragma unroll
         for (int i = 0; i < 4 * MM; ++i) acc[i] = 0.f;
     };
-    auto step = [&](const uint4 (&b)[4]) {
+    auto step = [&](const WV (&b)[4]) {
         uint4 av[MM];
 #pragma unroll
         for (int m = 0; m < MM; ++m) av[m] = *reinterpret_cast<const uint4*>(xa + ((size_t)m * KC + (ck >> 3)) * 16);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
+        for (int r = 0; r < 4; ++r) {
+            const uint4 w = widen_w(b[r]);
 #pragma unroll
             for (int m = 0; m < MM; ++m) {
-                dot2c(acc[r * MM + m], b[r].x, av[m].x); dot2c(acc[r * MM + m], b[r].y, av[m].y);
-                dot2c(acc[r * MM + m], b[r].z, av[m].z); dot2c(acc[r * MM + m], b[r].w, av[m].w);
+                dot2c(acc[r * MM + m], w.x, av[m].x); dot2c(acc[r * MM + m], w.y, av[m].y);
+                dot2c(acc[r * MM + m], w.z, av[m].z); dot2c(acc[r * MM + m], w.w, av[m].w);
             }
+        }
         __builtin_amdgcn_sched_barrier(0);
         ck += 512;
         if (ck >= K) { finish(); ck = 0; cu += stride; }
@@ -1866,19 +1909,21 @@ __global__ __launch_bounds__(512) void gemm_skinny_persist_kernel(GemmArgs p, in
 // NORM: the activations are RMSNorm(norm_x) * norm_w, staged as bf16 in LDS by stage_rmsnorm (K <= 4096, M <= 4) instead of read from
 // global memory.  act == 4 (R == 8 only): the wqkv epilogue of a decode step -- the workgroup owns rows d .. d+3 and d+64 .. d+67 of one
 // 128-row head slot, i.e. four rotate_half pairs, and writes q / the KV-cache rows directly (same arithmetic as the prefill epilogue).
-template <int MM, int R, bool NORM>
+template <int MM, int R, bool NORM, bool W8 = false>
 __global__ __launch_bounds__(256) void gemm_skinny_ksplit_kernel(GemmArgs p) {
+    using WT = typename SkinnyW<W8>::elem;
+    using WV = typename SkinnyW<W8>::vec;
     static_assert(R * MM == 16 || R * MM == 32, "the butterfly reduces 16 or 32 values per lane");
     extern __shared__ __attribute__((aligned(16))) char smem[];   // NORM: A as bf16 [MM][K]
     __shared__ float red[4][R * MM];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int KQ = p.K >> 2;                          // this wave's K range (K % 2048 == 0)
     const bf16* A = reinterpret_cast<const bf16*>(p.A) + (size_t)wv * KQ + lane * 8;
-    const bf16* W = reinterpret_cast<const bf16*>(p.W) + (size_t)wv * KQ + lane * 8;
+    const WT* W = reinterpret_cast<const WT*>(p.W) + (size_t)wv * KQ + lane * 8;
     const bool rope = R == 8 && p.act == 4;
     const long n0 = rope ? (long)(blockIdx.x >> 4) * 128 + (blockIdx.x & 15) * 4 : (long)blockIdx.x * R;
     auto row_of = [&](const int r) -> long { return rope ? n0 + (r & 3) + (r >> 2) * 64 : n0 + r; };
-    const bf16* wr[R];
+    const WT* wr[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) wr[r] = W + (size_t)min(row_of(r), (long)p.N - 1) * p.ldw;
     const bf16* ar[MM];
@@ -1887,7 +1932,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_ksplit_kernel(GemmArgs p) {
     float acc[R * MM];
 #pragma unroll
     for (int i = 0; i < R * MM; ++i) acc[i] = 0.f;
-    struct Buf { uint4 w[R], a[NORM ? 1 : MM]; };
+    struct Buf { WV w[R]; uint4 a[NORM ? 1 : MM]; };
     auto fill = [&](Buf& b, const int k) {
 #pragma unroll
         for (int r = 0; r < R; ++r) b.w[r] = load_w16(wr[r] + k);
@@ -1906,12 +1951,14 @@ __global__ __launch_bounds__(256) void gemm_skinny_ksplit_kernel(GemmArgs p) {
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int r = 0; r < R; ++r)
+        for (int r = 0; r < R; ++r) {
+            const uint4 w = widen_w(b.w[r]);
 #pragma unroll
             for (int m = 0; m < MM; ++m) {
-                dot2c(acc[r * MM + m], b.w[r].x, av[m].x); dot2c(acc[r * MM + m], b.w[r].y, av[m].y);
-                dot2c(acc[r * MM + m], b.w[r].z, av[m].z); dot2c(acc[r * MM + m], b.w[r].w, av[m].w);
+                dot2c(acc[r * MM + m], w.x, av[m].x); dot2c(acc[r * MM + m], w.y, av[m].y);
+                dot2c(acc[r * MM + m], w.z, av[m].z); dot2c(acc[r * MM + m], w.w, av[m].w);
             }
+        }
         __builtin_amdgcn_sched_barrier(0);
     };
     // Two register buffers rotate: one step of loads is in flight behind the one being multiplied (see gemm_skinny_kernel); the first loads are
@@ -1947,11 +1994,15 @@ __global__ __launch_bounds__(256) void gemm_skinny_ksplit_kernel(GemmArgs p) {
     if (tid >= R * MM) return;
     const int r = tid / MM, m = tid - r * MM;
     if (m >= p.M) return;
-    auto total = [&](const int i) { return (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]); };
+    // (W8: the row's scale multiplies the complete sum, after the four waves' partials are added)
+    auto total = [&](const int i, const long row) {
+        const float t = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+        if constexpr (W8) return t * p.col_scale[row]; else return t;
+    };
     if (rope) {
         if (r >= 4) return;                            // thread (r, m): the pair (row n0 + r, row n0 + 64 + r) of token m
         const long n1 = n0 + r, n2 = n1 + 64;
-        const float x1 = total(r * MM + m) + (p.bias ? p.bias[n1] : 0.f), x2 = total((r + 4) * MM + m) + (p.bias ? p.bias[n2] : 0.f);
+        const float x1 = total(r * MM + m, n1) + (p.bias ? p.bias[n1] : 0.f), x2 = total((r + 4) * MM + m, n2) + (p.bias ? p.bias[n2] : 0.f);
         const int slot = (int)(n1 >> 7), d = (int)(n1 & 127);
         const int gs = p.rope_G + 2, kv = slot / gs, g = slot - kv * gs;
         const int b = m / p.rope_S, sq = m - b * p.rope_S;
@@ -1974,7 +2025,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_ksplit_kernel(GemmArgs p) {
     }
     const long n = n0 + r;
     if (n >= p.N) return;
-    float v = total(tid);
+    float v = total(tid, n);
     if (p.bias) v += p.bias[n];
     if (p.act == 1) v = gelu_erf(v);
     else if (p.act == 2) v = fmaxf(v, 0.f);
@@ -1983,6 +2034,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_ksplit_kernel(GemmArgs p) {
     else reinterpret_cast<bf16*>(p.C)[(size_t)m * p.ldc + n] = (bf16)v;
 }
 
+template <bool W8 = false>   // W8: a.W holds e4m3 bytes, a.col_scale the rows' scales (ullsam_gemm_w8 / ullsam_decode_qkv_rope_w8); same dispatch, same grids
 static int launch_gemm_skinny(const GemmArgs& a, hipStream_t stream) {
     const bool normed = a.norm_x != nullptr;
     if (normed && (a.M > 4 || a.K > 4096 || a.K % 2048 != 0 || a.ldx % 4 != 0)) { ullsam_set_error("skinny GEMM: the fused RMSNorm prologue needs M <= 4, K <= 4096, K %% 2048 == 0 (M=%d K=%d)", a.M, a.K); return -1; }
@@ -1990,10 +2042,10 @@ static int launch_gemm_skinny(const GemmArgs& a, hipStream_t stream) {
     if (a.act == 4 || (a.act != 3 && a.N <= 8192 && a.K % 2048 == 0)) {  // narrow: K split over the waves of a workgroup
         const dim3 g4((unsigned)((a.N + 3) / 4)), g8((unsigned)((a.N + 7) / 8));
         const size_t lds = normed ? (size_t)4 * a.K * 2 : 0;
-        if (normed) gemm_skinny_ksplit_kernel<4, 8, true><<<g8, 256, lds, stream>>>(a);
-        else if (a.act == 4) gemm_skinny_ksplit_kernel<4, 8, false><<<g8, 256, 0, stream>>>(a);
-        else if (a.M > 4) gemm_skinny_ksplit_kernel<8, 4, false><<<g4, 256, 0, stream>>>(a);
-        else gemm_skinny_ksplit_kernel<4, 8, false><<<g8, 256, 0, stream>>>(a);   // (4 rows x 3 buffers, 4 x 2, 8 x 3 were measured within 1 % of this and removed)
+        if (normed) gemm_skinny_ksplit_kernel<4, 8, true, W8><<<g8, 256, lds, stream>>>(a);
+        else if (a.act == 4) gemm_skinny_ksplit_kernel<4, 8, false, W8><<<g8, 256, 0, stream>>>(a);
+        else if (a.M > 4) gemm_skinny_ksplit_kernel<8, 4, false, W8><<<g4, 256, 0, stream>>>(a);
+        else gemm_skinny_ksplit_kernel<4, 8, false, W8><<<g8, 256, 0, stream>>>(a);   // (4 rows x 3 buffers, 4 x 2, 8 x 3 were measured within 1 % of this and removed)
         ULLSAM_LAUNCH_CHECK();
         return 0;
     }
@@ -2013,21 +2065,21 @@ static int launch_gemm_skinny(const GemmArgs& a, hipStream_t stream) {
             const double waste = (double)(trips * per) / (double)waves;
             if (waste < best - 1e-9) { best = waste; W = w; }
         }
-        if (normed) gemm_skinny_persist_kernel<true><<<n_wg, W * 64, lds, stream>>>(a, (int)waves);
-        else gemm_skinny_persist_kernel<false><<<n_wg, W * 64, lds, stream>>>(a, (int)waves);
+        if (normed) gemm_skinny_persist_kernel<true, W8><<<n_wg, W * 64, lds, stream>>>(a, (int)waves);
+        else gemm_skinny_persist_kernel<false, W8><<<n_wg, W * 64, lds, stream>>>(a, (int)waves);
         ULLSAM_LAUNCH_CHECK();
         return 0;
     }
     const dim3 grid((unsigned)((waves + 3) / 4));
-    static PerDeviceOnce attr4, attr8;
+    static PerDeviceOnce attr4, attr8;   // (per instantiation of this launcher, i.e. per weight format)
     if (normed) {
-        gemm_skinny_kernel<4, true><<<grid, 256, lds, stream>>>(a);   // <= 32 KiB of LDS: no attribute needed
+        gemm_skinny_kernel<4, true, W8><<<grid, 256, lds, stream>>>(a);   // <= 32 KiB of LDS: no attribute needed
     } else if (MM == 4) {
-        if (attr4.first()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_skinny_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); }
-        gemm_skinny_kernel<4><<<grid, 256, lds, stream>>>(a);
+        if (attr4.first()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_skinny_kernel<4, false, W8>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); }
+        gemm_skinny_kernel<4, false, W8><<<grid, 256, lds, stream>>>(a);
     } else {
-        if (attr8.first()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_skinny_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); }
-        gemm_skinny_kernel<8><<<grid, 256, lds, stream>>>(a);
+        if (attr8.first()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_skinny_kernel<8, false, W8>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024); }
+        gemm_skinny_kernel<8, false, W8><<<grid, 256, lds, stream>>>(a);
     }
     ULLSAM_LAUNCH_CHECK();
     return 0;
@@ -2088,7 +2140,7 @@ static int gemm_impl(int dtype, const void* A, long lda, const void* W, long ldw
     // (the forced variants select TILE kernels; a launch with the RMSNorm prologue exists in the skinny kernels only and goes there whatever is forced)
     if ((variant == 0 || norm) && (act != 4 || (M <= 4 && K % 2048 == 0)) && dtype == ULLSAM_DT_BF16 && M <= 8 && K % 512 == 0 && lda % 8 == 0 && ldw % 8 == 0 &&
         (size_t)(M <= 4 ? 4 : 8) * K * 2 <= 144 * 1024 && (act != 3 || N % 128 == 0))
-        return launch_gemm_skinny(a, s);
+        return launch_gemm_skinny<false>(a, s);
     ULLSAM_CHECK(!norm, "ullsam_gemm: the RMSNorm prologue exists in the decode-step kernels only (bf16, M <= 4, K <= 4096; got M=%d K=%d)", M, K);
     const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256);
     // 256-row tiles run one per CU: use them when the last round of tiles is >= 74 % full (measured crossover, tools/gemm_bench.py:
@@ -2168,6 +2220,62 @@ extern "C" int ullsam_decode_qkv_rope(const void* a, const float* x, long ldx, c
     const int N = KVH * (G + 2) * 128;
     return gemm_impl(ULLSAM_DT_BF16, norm_w ? nullptr : a, K, W, ldw, q_out, (long)KVH * G * 128, 0, bias, nullptr, 0, 0, 4, B, N, K, nullptr, 0,
                      stream, &r, norm_w ? &n : nullptr);
+}
+
+// Decode step on e4m3 weights: the skinny kernels' W8 forms.  No tile kernel reads this format, so every shape launch_gemm_skinny does not take
+// is an error here (the callers keep the bf16 weights for those).
+static int gemm_w8_impl(const char* who, const void* A, const NormPrologue* norm, const void* W8, long ldw, const float* w_scale, void* C, long ldc, int out_f32,
+                        const float* bias, const float* residual, long ldr, int act, int M, int N, int K, void* stream, const RopeEpilogue* rope) {
+    ULLSAM_CHECK(W8 && w_scale && C, "%s: null weights, scales or output", who);
+    ULLSAM_CHECK(M > 0 && M <= 8 && N > 0 && K > 0 && K % 512 == 0, "%s: decode-step shapes only (1 <= M <= 8, K %% 512 == 0; got M=%d N=%d K=%d)", who, M, N, K);
+    ULLSAM_CHECK((size_t)(M <= 4 ? 4 : 8) * K * 2 <= 144 * 1024, "%s: K=%d: the activation rows do not fit the LDS", who, K);
+    ULLSAM_CHECK(act >= 0 && act <= 4 && (act == 4) == (rope != nullptr), "%s: bad act %d", who, act);
+    ULLSAM_CHECK(((uintptr_t)W8 & 7) == 0 && ldw % 8 == 0 && ldw >= K, "%s: weight rows must be 8-byte aligned (ldw=%ld)", who, ldw);
+    if (act == 3) ULLSAM_CHECK(N % 128 == 0 && !bias && !residual, "%s: swiglu needs N %% 128 == 0, no bias / residual", who);
+    GemmArgs a{};   // (every field the tile kernels alone read stays zero / null)
+    if (rope) {
+        a.rope_pos = rope->pos; a.rope_cos = rope->cos; a.rope_sin = rope->sin; a.rope_q = rope->q; a.rope_k = rope->k; a.rope_v = rope->v;
+        a.rope_S = rope->S; a.rope_KVH = rope->KVH; a.rope_G = rope->G; a.rope_cap = rope->cap; a.rope_pos0 = rope->pos0; a.rope_rows = rope->rows;
+    }
+    if (norm) {
+        ULLSAM_CHECK(norm->x && norm->w && ((uintptr_t)norm->x & 15) == 0 && ((uintptr_t)norm->w & 15) == 0 && norm->ldx % 4 == 0,
+                     "%s: the RMSNorm prologue needs 16-byte aligned fp32 rows and weight", who);
+        a.norm_x = norm->x; a.norm_w = norm->w; a.norm_eps = norm->eps; a.ldx = norm->ldx;
+    } else {
+        ULLSAM_CHECK(A && ((uintptr_t)A & 15) == 0, "%s: bf16 activations must be 16-byte aligned", who);
+    }
+    a.A = A; a.W = W8; a.C = C; a.bias = bias; a.residual = residual; a.col_scale = w_scale;
+    a.M = M; a.N = N; a.K = K;
+    a.lda = K; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr;
+    a.act = act; a.out_f32 = out_f32;
+    a.group_m = g_group_m; a.ksplit = 1;
+    return launch_gemm_skinny<true>(a, reinterpret_cast<hipStream_t>(stream));   // (its own checks: prologue M <= 4, K <= 4096, K % 2048; RoPE M <= 4, K % 2048, N % 128)
+}
+
+// ullsam_gemm / ullsam_gemm_rmsnorm for a decode step on e4m3 weights: out = act((a @ W8^T) * w_scale + bias) (+ residual), a = the bf16 rows
+// `A` [M, K] (norm_w NULL) or bf16(RMSNorm(x) * norm_w) of the fp32 rows `x` (M <= 4, K <= 4096).  modeling_internlm2.py:261-264 (w13 / w2),
+// :421 (wo), :1081-1082 (the LM head).
+extern "C" int ullsam_gemm_w8(const void* A, const float* x, long ldx, const float* norm_w, float eps, const void* W8, long ldw, const float* w_scale,
+                              void* C, long ldc, int out_f32, const float* bias, const float* residual, long ldr, int act, int M, int N, int K,
+                              void* stream) {
+    ULLSAM_CHECK(act != 4, "ullsam_gemm_w8: act 4 is ullsam_decode_qkv_rope_w8");
+    NormPrologue n{x, ldx, norm_w, eps};
+    return gemm_w8_impl("ullsam_gemm_w8", norm_w ? nullptr : A, norm_w ? &n : nullptr, W8, ldw, w_scale, C, ldc, out_f32, bias, residual, ldr, act, M, N, K, stream, nullptr);
+}
+
+// ullsam_decode_qkv_rope on e4m3 weights (modeling_internlm2.py:341-426: wqkv, head split, RoPE, cache append).
+extern "C" int ullsam_decode_qkv_rope_w8(const void* a, const float* x, long ldx, const float* norm_w, float eps, const void* W8, long ldw,
+                                         const float* w_scale, const float* bias, int B, int K, int KVH, int G, const int* pos, const float* cos_tab,
+                                         const float* sin_tab, int tab_rows, void* q_out, void* k_cache, void* v_cache, int cap, int cache_pos0,
+                                         void* stream) {
+    ULLSAM_CHECK(B > 0 && B <= 4 && KVH > 0 && G > 0 && tab_rows > 0 && K > 0 && K % 2048 == 0, "ullsam_decode_qkv_rope_w8: B=%d (1..4) K=%d (%% 2048)", B, K);
+    ULLSAM_CHECK(cache_pos0 >= 0 && cache_pos0 + 1 <= cap, "ullsam_decode_qkv_rope_w8: cache overflow (%d + 1 > %d)", cache_pos0, cap);
+    ULLSAM_CHECK(pos && cos_tab && sin_tab && q_out && k_cache && v_cache, "ullsam_decode_qkv_rope_w8: null argument");
+    RopeEpilogue r{pos, cos_tab, sin_tab, q_out, k_cache, v_cache, 1, KVH, G, cap, cache_pos0, tab_rows};
+    NormPrologue n{x, ldx, norm_w, eps};
+    const int N = KVH * (G + 2) * 128;
+    return gemm_w8_impl("ullsam_decode_qkv_rope_w8", norm_w ? nullptr : a, norm_w ? &n : nullptr, W8, ldw, w_scale, q_out, (long)KVH * G * 128, 0, bias, nullptr, 0, 4, B, N, K,
+                        stream, &r);
 }
 
 // wqkv GEMM of InternLM2Attention with the head split, RoPE and the KV-cache append in its epilogue (modeling_internlm2.py:359-388):

@@ -377,3 +377,61 @@ extern "C" int ullsam_rows_fp8(const void* in, int in_dtype, long in_stride, voi
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Weight-only e4m3 for the LLM's decode steps (gemm.hip: the W8 forms of the gemm_skinny_* kernels; modeling_internlm2.py:261-264,341-426,
+// 1081-1082 are the linears it feeds).  Per row: scale = the smallest power of two with amax / scale <= 448 (not amax / 448 as above: q * scale is
+// then exact in bf16 for a bf16 weight, so the fp8 decode is the bf16 decode on the dequantised weights), then the same saturating
+// round-to-nearest-even conversion.  One wave per row, two passes over the row (rows of any length: w2 has K = 14336).
+// amax = f * 2^e with f in [0.5, 1), 448 = 0.875 * 2^9: scale = 2^(e - 9) if f <= 0.875 else 2^(e - 8), never below 2^-126; a zero row gets 1.
+// ---------------------------------------------------------------------------------------------------------------
+template <typename TI>
+__global__ __launch_bounds__(256) void rows_fp8_pow2_kernel(const TI* __restrict__ in, long in_stride, unsigned char* __restrict__ out, long out_stride,
+                                                           float* __restrict__ scale, long rows, int D) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const TI* x = in + row * in_stride;
+    const int nv = D >> 2;
+    float amax = 0.f;
+    for (int idx = lane; idx < nv; idx += 64) {
+        const float4 v = load4(x + idx * 4);
+        amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+    }
+    amax = wave_max(amax);
+    float sc = 1.0f, inv = 1.0f;
+    if (amax > 0.f) {
+        int e;
+        const float f = frexpf(amax, &e);
+        const int s = max((f <= 0.875f ? e - 9 : e - 8), -126);
+        sc = ldexpf(1.0f, s);
+        inv = ldexpf(1.0f, -s);
+    }
+    if (lane == 0) scale[row] = sc;
+    unsigned int* y = reinterpret_cast<unsigned int*>(out + row * out_stride);
+    for (int idx = lane; idx < nv; idx += 64) {
+        const float4 v = load4(x + idx * 4);
+        const float q0 = fminf(fmaxf(v.x * inv, -448.f), 448.f), q1 = fminf(fmaxf(v.y * inv, -448.f), 448.f);
+        const float q2 = fminf(fmaxf(v.z * inv, -448.f), 448.f), q3 = fminf(fmaxf(v.w * inv, -448.f), 448.f);
+        int pk = __builtin_amdgcn_cvt_pk_fp8_f32(q0, q1, 0, false);
+        pk = __builtin_amdgcn_cvt_pk_fp8_f32(q2, q3, pk, true);
+        y[idx] = (unsigned int)pk;
+    }
+}
+
+// in: fp32 / bf16 [rows, D] (in_dtype 0 / 1, row stride in elements); out: e4m3 bytes [rows, out_stride]; scale fp32 [rows], powers of two.
+extern "C" int ullsam_rows_fp8_pow2(const void* in, int in_dtype, long in_stride, void* out, long out_stride, float* scale, long rows, int D,
+                                    void* stream) {
+    ULLSAM_CHECK(in_dtype == ULLSAM_DT_F32 || in_dtype == ULLSAM_DT_BF16, "ullsam_rows_fp8_pow2: bad dtype %d", in_dtype);
+    ULLSAM_CHECK(D > 0 && D % 4 == 0 && rows >= 0 && rows <= 4l * 0x7fffffff, "ullsam_rows_fp8_pow2: D=%d must be a positive multiple of 4", D);
+    ULLSAM_CHECK(in_stride >= D && in_stride % 4 == 0 && ((uintptr_t)in & (in_dtype == ULLSAM_DT_F32 ? 15 : 7)) == 0, "ullsam_rows_fp8_pow2: input rows must be aligned groups of 4 elements");
+    ULLSAM_CHECK(out_stride >= D && out_stride % 4 == 0 && ((uintptr_t)out & 3) == 0, "ullsam_rows_fp8_pow2: output rows must be 4-byte aligned");
+    ULLSAM_CHECK(in && out && scale, "ullsam_rows_fp8_pow2: null argument");
+    if (rows == 0) return 0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (in_dtype == ULLSAM_DT_F32) rows_fp8_pow2_kernel<float><<<grid, 256, 0, s>>>(reinterpret_cast<const float*>(in), in_stride, reinterpret_cast<unsigned char*>(out), out_stride, scale, rows, D);
+    else rows_fp8_pow2_kernel<bf16><<<grid, 256, 0, s>>>(reinterpret_cast<const bf16*>(in), in_stride, reinterpret_cast<unsigned char*>(out), out_stride, scale, rows, D);
+    ULLSAM_LAUNCH_CHECK();
+    return 0;
+}

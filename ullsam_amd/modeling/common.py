@@ -77,6 +77,11 @@ class Linear(Packed):
         pair = self.pk("w8", self.weight, lambda: ops.rows_fp8(self.weight.detach().contiguous()))
         return pair
 
+    def w8d(self):
+        """(e4m3 bytes [out, in], fp32 power-of-two per-output-channel scales [out]) for the weight-only fp8 decode kernels (ops.gemm_w8); the weight itself
+        stays (prefill reads it).  Quantised once per weight version."""
+        return self.pk("w8d", self.weight, lambda: ops.rows_fp8_pow2(self.weight.detach().contiguous()))
+
     def tok(self, x: torch.Tensor, act: int = ops.ACT_NONE, res: Optional[torch.Tensor] = None) -> torch.Tensor:
         """fp32 token-side application (decoder tokens, hypernetwork / IoU MLPs): one wave per output for a handful of rows,
         the row-blocked kernel over the transposed weight from 64 rows up (many prompts)."""

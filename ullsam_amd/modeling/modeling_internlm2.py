@@ -52,6 +52,10 @@ class InternLM2MLP(Packed):
     def w13(self, dt):
         return self.pk("w13", (self.w1.weight, self.w3.weight), lambda: pack_w13(self.w1.weight.detach().to(dt), self.w3.weight.detach().to(dt)))
 
+    def w13_w8d(self, dt):
+        """e4m3 bytes + per-row scales of the PACKED [gate | up] rows (quantised after packing: the rows the kernel reads are the rows that were scaled)."""
+        return self.pk("w13:w8d", (self.w1.weight, self.w3.weight), lambda: ops.rows_fp8_pow2(self.w13(dt)))
+
 
 class InternLM2Attention(Packed):
     def __init__(self, config: InternLM2Config):
@@ -128,6 +132,7 @@ class InternLM2Model(Packed):
         self._rope = None
         self.collect_all_hidden_states = False
         self.fuse_decode = True   # decode steps use the fused norm / RoPE launches (tests switch it off to compare with the separate kernels)
+        self.fp8_decode = False   # set through InternLM2ForCausalLM.fp8_decode (documented there)
         self.stage_probe = None   # diagnostic tap: stage_probe(layer_index, x) with the fp32 residual stream [B*S, D] after every layer
 
     def get_input_embeddings(self):
@@ -174,7 +179,8 @@ class InternLM2Model(Packed):
     # -- the layer stack -------------------------------------------------------------------------------------------
     def run_layers(self, x: torch.Tensor, B: int, S: int, pos: torch.Tensor, key_mask: Optional[torch.Tensor],
                    cache: Optional[KVCache], collect: Optional[list] = None) -> torch.Tensor:
-        """x fp32 [B*S, D] (updated in place) -> post-final-norm hidden [B*S, D] in the model dtype."""
+        """x fp32 [B*S, D] (updated in place) -> post-final-norm hidden [B*S, D] in the model dtype.  With `fp8_decode` a fused decode step streams the
+        e4m3 packs of wqkv / wo / w13 / w2 (see InternLM2ForCausalLM.fp8_decode); everything else reads the weights in the model dtype."""
         cfg = self.config
         dt = self.compute_dtype
         H, KVH = cfg.num_attention_heads, cfg.num_key_value_heads
@@ -188,12 +194,17 @@ class InternLM2Model(Packed):
             tmp_v = torch.empty_like(tmp_k)
         # a decode step of <= 4 sequences (bf16, head_dim 128, hidden <= 4096): norms and RoPE ride in the GEMMs' prologue / epilogue
         fused = S == 1 and cache is not None and hd == 128 and ops.decode_fusable(B, cfg.hidden_size, dt) and self.fuse_decode
+        w8 = bool(getattr(self, "fp8_decode", False)) and fused and x.is_cuda   # weight-only e4m3 streams; a wo / w2 whose K the kernels decline stays bf16
+        w8_wo, w8_w2 = w8 and ops.decode_w8_ok(B, H * hd), w8 and ops.decode_w8_ok(B, cfg.intermediate_size)
         for li, layer in enumerate(self.layers):
             if collect is not None:
                 collect.append(x.reshape(B, S, -1).to(dt))
             at, ff = layer.attention, layer.feed_forward
             kc, vc = (cache.k[li], cache.v[li]) if cache is not None else (tmp_k, tmp_v)
-            if fused:   # decode step: RMSNorm -> wqkv -> head split + RoPE + KV append is ONE launch (the norm runs while the weight stream starts)
+            if w8:
+                q = ops.decode_qkv_rope_w8(x, layer.attention_norm.w(), layer.attention_norm.variance_epsilon, *at.wqkv.w8d(), at.wqkv.b(), kc, vc,
+                                           pos, cos, sin, B, KVH, G, past)
+            elif fused:   # decode step: RMSNorm -> wqkv -> head split + RoPE + KV append is ONE launch (the norm runs while the weight stream starts)
                 q = ops.decode_qkv_rope(x, layer.attention_norm.w(), layer.attention_norm.variance_epsilon, at.wqkv.w(dt), at.wqkv.b(), kc, vc,
                                         pos, cos, sin, B, KVH, G, past)
             else:
@@ -211,13 +222,21 @@ class InternLM2Model(Packed):
                 cap = kc.shape[2]
                 a = ops.naive_attention(q, kc, vc, B, H, KVH, hd, 1, Sk, (H * hd, H * hd, hd), (KVH * cap * hd, hd, cap * hd),
                                         (KVH * cap * hd, hd, cap * hd), (H * hd, H * hd, hd), hd ** -0.5, key_mask=key_mask)
-            ops.gemm(a, at.wo.w(dt), at.wo.b(), residual=x, out_f32=True, out=x)
-            if fused:
+            if w8_wo:
+                ops.gemm_w8(a, *at.wo.w8d(), at.wo.b(), residual=x, out_f32=True, out=x)
+            else:
+                ops.gemm(a, at.wo.w(dt), at.wo.b(), residual=x, out_f32=True, out=x)
+            if w8:
+                hmid = ops.gemm_w8(x, *ff.w13_w8d(dt), act=ops.ACT_SWIGLU, norm_w=layer.ffn_norm.w(), eps=layer.ffn_norm.variance_epsilon)
+            elif fused:
                 hmid = ops.gemm_rmsnorm(x, layer.ffn_norm.w(), layer.ffn_norm.variance_epsilon, ff.w13(dt), act=ops.ACT_SWIGLU)
             else:
                 xn = ops.norm(x, layer.ffn_norm.w(), None, layer.ffn_norm.variance_epsilon, dt, rms=True)
                 hmid = ops.gemm(xn, ff.w13(dt), act=ops.ACT_SWIGLU)
-            ops.gemm(hmid, ff.w2.w(dt), None, residual=x, out_f32=True, out=x)
+            if w8_w2:
+                ops.gemm_w8(hmid, *ff.w2.w8d(), None, residual=x, out_f32=True, out=x)
+            else:
+                ops.gemm(hmid, ff.w2.w(dt), None, residual=x, out_f32=True, out=x)
             if self.stage_probe is not None:
                 self.stage_probe(li, x)
         if cache is not None:
@@ -276,6 +295,24 @@ class InternLM2ForCausalLM(Packed):
         self.model = InternLM2Model(config)
         self.vocab_size = config.vocab_size
         self.output = Linear(config.hidden_size, config.vocab_size, bias=False)
+        # Weight-only fp8 (OCP e4m3, one power-of-two scale per output channel) for the decode steps of a bf16 model: the steps that run on the fused
+        # decode kernels (one token per sequence behind a cache, <= 4 sequences, hidden <= 4096) stream e4m3 copies of wqkv / wo / w13 / w2 and of the
+        # LM head -- half the bytes of a memory-bound step.  Prefill, training, fp32 models and every other shape read the bf16 weights, which stay
+        # (about half the LLM's bf16 bytes in extra memory; checkpoint.prepack(fp8_decode=True) builds the copies up front).  Off by default.
+        self.fp8_decode = False
+
+    @property
+    def fp8_decode(self) -> bool:
+        return bool(getattr(self.model, "fp8_decode", False))
+
+    @fp8_decode.setter
+    def fp8_decode(self, on: bool):
+        self.model.fp8_decode = bool(on)   # kept on the layer stack: InternLM2Model.forward is called on its own too (the token loop calls it per step)
+
+    @fp8_decode.deleter
+    def fp8_decode(self):
+        if "fp8_decode" in self.model.__dict__:
+            del self.model.fp8_decode
 
     def get_input_embeddings(self):
         return self.model.tok_embeddings
@@ -283,10 +320,13 @@ class InternLM2ForCausalLM(Packed):
     def get_output_embeddings(self):
         return self.output
 
-    def lm_head(self, hidden: torch.Tensor) -> torch.Tensor:
-        """logits = output(hidden).float()  (:1081-1082); hidden [..., D] in the model dtype -> fp32 [..., V]."""
+    def lm_head(self, hidden: torch.Tensor, prefill: bool = False) -> torch.Tensor:
+        """logits = output(hidden).float()  (:1081-1082); hidden [..., D] in the model dtype -> fp32 [..., V].  With fp8_decode, <= 4 rows (a decode step's)
+        read the head's e4m3 copy; prefill: the rows are prompt positions (the prompt's last one in generate) and read the bf16 head whatever the switch."""
         dt = self.model.compute_dtype
         h2 = hidden.reshape(-1, hidden.shape[-1]).contiguous()
+        if not prefill and self.fp8_decode and self.model.fuse_decode and h2.is_cuda and ops.decode_fusable(h2.shape[0], h2.shape[1], dt):
+            return ops.gemm_w8(ops.cast(h2, dt), *self.output.w8d(), None, out_f32=True).reshape(*hidden.shape[:-1], self.vocab_size)
         return ops.gemm(ops.cast(h2, dt), self.output.w(dt), None, out_f32=True).reshape(*hidden.shape[:-1], self.vocab_size)
 
     @torch.no_grad()
@@ -297,7 +337,8 @@ class InternLM2ForCausalLM(Packed):
                          output_hidden_states=output_hidden_states)
         hidden = out.last_hidden_state
         loss = None
-        logits_fn = lambda: self.lm_head(hidden)
+        prefill = not (hidden.shape[1] == 1 and past_key_values is not None)   # (one token per sequence behind a cache is what run_layers takes for a decode step)
+        logits_fn = lambda: self.lm_head(hidden, prefill=prefill)
         logits = None
         if labels is not None:
             logits = logits_fn()
@@ -356,7 +397,7 @@ class InternLM2ForCausalLM(Packed):
         mask_full[:, :S] = mask
         pos_next = mask.sum(-1, keepdim=True).to(torch.int32)  # = cumsum(mask)[:, -1]: position id of the next token (cumsum - 1 of the extended mask)
         for step in range(max_new_tokens):
-            logits = self.lm_head(h_last)  # fp32 [B, V], last position only
+            logits = self.lm_head(h_last, prefill=step == 0 and S > 1)  # fp32 [B, V], last position only
             if do_sample:
                 tok = _sample(logits, temperature, top_k, top_p)
             else:

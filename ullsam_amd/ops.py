@@ -489,6 +489,11 @@ def decode_fusable(M: int, K: int, dtype: torch.dtype) -> bool:
     return dtype == torch.bfloat16 and 1 <= M <= 4 and K <= 4096 and K % 2048 == 0
 
 
+def decode_w8_ok(M: int, K: int) -> bool:
+    """Shapes ullsam_gemm_w8 takes: exactly those at which a bf16 ops.gemm runs on the decode-step (skinny) kernels (csrc/gemm.hip gemm_impl)."""
+    return 1 <= M <= 8 and K % 512 == 0 and (4 if M <= 4 else 8) * K * 2 <= 144 * 1024
+
+
 def gemm_rmsnorm(x: torch.Tensor, norm_w: torch.Tensor, eps: float, w: torch.Tensor, act: int = ACT_NONE) -> torch.Tensor:
     """act(bf16(RMSNorm(x) * norm_w) @ w^T) for a decode step's M <= 4 fp32 rows: the norm is computed while the weight stream starts."""
     _chk(x, "x", torch.float32); _chk(norm_w, "norm_w", torch.float32); _chk(w, "w", torch.bfloat16)
@@ -519,6 +524,72 @@ def decode_qkv_rope(x: torch.Tensor, norm_w: Optional[torch.Tensor], eps: float,
     _lib.call("ullsam_decode_qkv_rope", None if norm_w is not None else x.data_ptr(), x.data_ptr() if norm_w is not None else None, K, _p(norm_w),
               float(eps), wqkv.data_ptr(), K, _p(bias), B, K, KVH, G, pos.data_ptr(), cos_tab.data_ptr(), sin_tab.data_ptr(), cos_tab.shape[0],
               q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.shape[2], cache_pos0, _stream())
+    return q
+
+
+def rows_fp8_pow2(w: torch.Tensor):
+    """Weight-only e4m3 for the decode steps: w fp32 / bf16 [N, K] -> (uint8 [N, K] holding e4m3 bytes, fp32 scales [N]); per row the scale is the
+    smallest power of two with amax / scale <= 448 (1 for a zero row), so `q * scale` of a bf16 weight is exact in bf16."""
+    _chk(w, "w")
+    assert w.dim() == 2 and w.shape[1] % 4 == 0, w.shape
+    N, K = w.shape
+    q = torch.empty((N, K), dtype=torch.uint8, device=w.device)
+    sc = torch.empty((N,), dtype=torch.float32, device=w.device)
+    _lib.call("ullsam_rows_fp8_pow2", w.data_ptr(), dt_code(w.dtype), K, q.data_ptr(), K, sc.data_ptr(), N, K, _stream())
+    return q, sc
+
+
+def gemm_w8(a: torch.Tensor, w8: torch.Tensor, w_scale: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+            act: int = ACT_NONE, out_f32: bool = False, out: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0) -> torch.Tensor:
+    """ops.gemm / ops.gemm_rmsnorm of a decode step (M <= 8 rows) on e4m3 weights: act((h @ w8^T) * w_scale + bias) + residual, where h is the bf16 `a`
+    [M, K] (norm_w None) or bf16(RMSNorm(a) * norm_w) of the fp32 rows `a` (M <= 4, K <= 4096).  Shapes the decode kernels do not take raise."""
+    _chk(a, "a", torch.float32 if norm_w is not None else torch.bfloat16); _chk(w8, "w8", torch.uint8); _chk(w_scale, "w_scale", torch.float32)
+    M, K = a.shape
+    N = w8.shape[0]
+    assert w8.shape[1] == K and w_scale.numel() == N, (a.shape, w8.shape, w_scale.shape)
+    n_out = N // 2 if act == ACT_SWIGLU else N
+    odt = torch.float32 if out_f32 else torch.bfloat16
+    if out is None:
+        out = torch.empty((M, n_out), dtype=odt, device=a.device)
+    else:
+        _chk(out, "out", odt)
+        assert out.shape == (M, n_out)
+    if bias is not None:
+        _chk(bias, "bias", torch.float32)
+        assert bias.numel() == N
+    ldr = 0
+    if residual is not None:
+        _chk(residual, "residual", torch.float32)
+        assert residual.shape == (M, n_out)
+        ldr = residual.shape[-1]
+    if norm_w is not None:
+        _chk(norm_w, "norm_w", torch.float32)
+        assert norm_w.numel() == K
+    _lib.call("ullsam_gemm_w8", None if norm_w is not None else a.data_ptr(), a.data_ptr() if norm_w is not None else None, K, _p(norm_w), float(eps),
+              w8.data_ptr(), K, w_scale.data_ptr(), out.data_ptr(), n_out, int(out_f32), _p(bias), _p(residual), ldr, act, M, N, K, _stream())
+    return out
+
+
+def decode_qkv_rope_w8(x: torch.Tensor, norm_w: Optional[torch.Tensor], eps: float, wqkv8: torch.Tensor, w_scale: torch.Tensor, bias: Optional[torch.Tensor],
+                       k_cache, v_cache, pos, cos_tab, sin_tab, B, KVH, G, cache_pos0) -> torch.Tensor:
+    """decode_qkv_rope on e4m3 wqkv bytes [KVH * (G + 2) * 128, K] with their per-row scales."""
+    _chk(wqkv8, "wqkv8", torch.uint8); _chk(w_scale, "w_scale", torch.float32); _chk(pos, "position_ids", torch.int32)
+    _chk(cos_tab, "cos", torch.float32); _chk(sin_tab, "sin", torch.float32)
+    _chk(k_cache, "k_cache", torch.bfloat16); _chk(v_cache, "v_cache", torch.bfloat16)
+    _chk(x, "x", torch.float32 if norm_w is not None else torch.bfloat16)
+    K = x.shape[1]
+    N = KVH * (G + 2) * 128
+    assert wqkv8.shape == (N, K) and w_scale.numel() == N and x.shape[0] == B and cos_tab.shape[1] == 128 and decode_fusable(B, K, torch.bfloat16)
+    assert pos.numel() >= B and k_cache.shape[0] >= B and k_cache.shape[1] == KVH and k_cache.shape[3] == 128 and v_cache.shape == k_cache.shape
+    if bias is not None:
+        _chk(bias, "bias", torch.float32)
+        assert bias.numel() == N
+    if norm_w is not None:
+        _chk(norm_w, "norm_w", torch.float32)
+    q = torch.empty((B, KVH * G * 128), dtype=torch.bfloat16, device=x.device)
+    _lib.call("ullsam_decode_qkv_rope_w8", None if norm_w is not None else x.data_ptr(), x.data_ptr() if norm_w is not None else None, K, _p(norm_w),
+              float(eps), wqkv8.data_ptr(), K, w_scale.data_ptr(), _p(bias), B, K, KVH, G, pos.data_ptr(), cos_tab.data_ptr(), sin_tab.data_ptr(),
+              cos_tab.shape[0], q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.shape[2], cache_pos0, _stream())
     return q
 
 
