@@ -18,6 +18,8 @@ def T(x):
 
 
 def test_amg_helpers_bit_exact_vs_reference_vectors():
+    """The one-launch helpers of utils/amg.py against vectors recorded from the reference: calculate_stability_score (ullsam_stability_score),
+    batched_mask_to_box (ullsam_mask_to_box), mask_to_rle_pytorch (ullsam_rle_pack + ullsam_rle_emit); bit-exact."""
     from ullsam_amd.utils import amg as A
     g = U.gold("amg")
     logits = T(g["logits"])
@@ -46,6 +48,7 @@ def test_amg_helpers_bit_exact_vs_reference_vectors():
 
 
 def test_rle_full_size_and_edge_cases():
+    """mask_to_rle_pytorch (ullsam_rle_pack: transpose + change words, ullsam_rle_emit: run edges) at full size and on empty / full / one-pixel masks."""
     from ullsam_amd.utils import amg as A
     rng = np.random.default_rng(0)
     m = rng.random((5, 1024, 1024)) > 0.5          # worst case: ~half a million runs per mask
@@ -81,6 +84,7 @@ def test_rle_and_box_ragged_shapes(shape):
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 700])
 def test_box_nms_matches_oracle(n):
+    """box_nms (the suppression bit matrix of ullsam_nms_mask + the host's greedy pass) against the oracle's torchvision-style NMS."""
     from ullsam_amd.utils import amg as A
     rng = np.random.default_rng(n)
     xy = rng.uniform(0, 900, (n, 2)).astype(np.float32)
@@ -127,7 +131,7 @@ def _smooth_logits(rng, m, h, w, cells=6):
     dict(low=(3, 32, 32), S=128, inp=(128, 128), crop=[0, 0, 70, 70], orig=(70, 70)),                   # partial 64-row block
 ])
 def test_fused_postprocess_equals_the_helper_chain(case):
-    """postprocess_low_res == postprocess_masks -> calculate_stability_score -> threshold -> batched_mask_to_box -> uncrop_masks ->
+    """postprocess_low_res (ullsam_amg_postprocess, one launch) == postprocess_masks -> calculate_stability_score -> threshold -> batched_mask_to_box -> uncrop_masks ->
     mask_to_rle_pytorch, the chain the reference's helpers were written for."""
     from ullsam_amd import ops
     from ullsam_amd.utils import amg as A
@@ -482,7 +486,7 @@ def test_generate_batch_equals_generate_per_tile_under_rccl_world_1():
 @pytest.mark.parametrize("P,T,shared", [(16, 7, True), (8, 9, False), (5, 16, True), (1, 7, False)])
 def test_fused_image_to_token_block_equals_the_separate_launches(P, T, shared):
     """transformer.FUSED_I2T (default for bf16 from 1024 image tokens): the image -> token half of a two-way block -- q projection, attention over the
-    T tokens, output projection + fp32 residual, norm4 with its three outputs -- as ONE kernel (csrc/decoder.hip i2t_block_kernel) against the five
+    T tokens, output projection + fp32 residual, norm4 with its three outputs -- as ONE kernel (ullsam_i2t_block: csrc/decoder.hip i2t_block_kernel) against the five
     launches it replaces, through TwoWayTransformer.forward_tokens on random weights: same bf16 roundings at the same places, sums in another
     order.  Both image-side layouts: one image shared by all prompts (layer 0 broadcast) and one stream per prompt; a ragged prompt count."""
     from ullsam_amd.modeling import transformer as TR
@@ -598,7 +602,7 @@ def test_fused_first_upscaling_layernorm_gelu_equals_the_separate_launches(rows)
 def test_fused_token_side_of_the_two_way_blocks_equals_the_separate_launches(P, T, shared):
     """transformer.FUSED_TOK (default for bf16): the token side of a two-way block -- self attention with its four projections, norm1, the token -> image q
     projection | the token -> image out projection, norm2, the MLP, norm3, the image -> token k / v projections -- as TWO launches around the token -> image
-    attention (csrc/dectok.hip: one workgroup per prompt, bf16 MFMA with fp32 accumulation, every activation as TWO bf16 terms = ~17 bits) against the ~18 fp32 launches it replaces, through TwoWayTransformer.forward_tokens on random weights.  The AMG batch shape (64 prompts on one
+    attention (ullsam_dec_tok_attn and ullsam_dec_tok_mlp, csrc/dectok.hip: one workgroup per prompt, bf16 MFMA with fp32 accumulation, every activation as TWO bf16 terms = ~17 bits) against the ~18 fp32 launches it replaces, through TwoWayTransformer.forward_tokens on random weights.  The AMG batch shape (64 prompts on one
     shared image), the bench's (4 images, one prompt each), the largest token count, one prompt, a prompt count that is not a multiple of anything."""
     from ullsam_amd.modeling import transformer as TR
     torch.manual_seed(P * 131 + T)
@@ -642,7 +646,7 @@ def test_fused_token_side_of_the_two_way_blocks_equals_the_separate_launches(P, 
 @pytest.mark.parametrize("P", [64, 4, 1, 19])
 def test_fused_hypernetwork_and_iou_heads_equal_the_separate_launches(P):
     """mask_decoder.FUSED_HEADS (default for bf16): the four hypernetwork MLPs and the IoU head (mask_decoder.py:141-149,154-176; 15 linears) as one launch
-    (csrc/dectok.hip dec_heads_kernel) against the 15 fp32 launches: through MaskDecoder.predict_masks_tokens on random weights."""
+    (ullsam_dec_heads: csrc/dectok.hip dec_heads_kernel) against the 15 fp32 launches: through MaskDecoder.predict_masks_tokens on random weights."""
     from ullsam_amd.modeling import mask_decoder as MD
     from ullsam_amd.build_sam import _build_sam
     torch.manual_seed(P)

@@ -92,6 +92,7 @@ def _check_labels(masks):
 # ---- 1. labels ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_label_regions_matches_scipy(shape):
+    """utils.amg.label_regions (ullsam_label_regions) against the 8-connected reference labelling of this file, every pattern, as one batch and mask by mask."""
     masks = [f(*shape) for f in PATTERNS.values()]
     _check_labels(masks)                       # all patterns as one batch: a mask must not leak labels into its neighbour
     for m in masks[:4]:
@@ -139,6 +140,7 @@ def _check_removal(masks, thresholds=THRESHOLDS, modes=("holes", "islands")):
 
 @pytest.mark.parametrize("shape", [(1, 1), (1, 300), (300, 1), (64, 64), (517, 643)], ids=lambda s: f"{s[0]}x{s[1]}")
 def test_remove_small_regions_matches_host(shape):
+    """utils.amg.remove_small_regions_batched (ullsam_remove_small_regions) against the host form of amg.py:267-291, holes and islands."""
     masks = [f(*shape) for f in PATTERNS.values()]
     masks.append(_speckled_disc(*shape, shape[0] / 2, shape[1] / 2, min(shape) / 3, 5, p=0.01)[0])
     n_changed = _check_removal(masks)

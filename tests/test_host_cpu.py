@@ -716,3 +716,25 @@ def test_every_training_entry_point_is_named_by_a_test():
     text = "".join(open(os.path.join(here, f)).read() for f in sorted(os.listdir(here)) if f.startswith("test_") and f.endswith(".py"))
     missing = [s for s in names if not re.search(r"\b" + s + r"\b", text)]
     assert not missing, f"training entry points no test names: {missing}"
+
+
+def test_every_inference_entry_point_is_reached_by_a_test():
+    """Each inference entry point of include/ullsam_hip.h (every ullsam_* symbol that is not ullsam_train_*, the switches and queries below aside) is
+    reached directly by some test module: its name appears there (a _lib.call or a lib.<symbol>), or a wrapper of ullsam_amd/ops.py whose body names
+    it is called as ops.<wrapper>( -- so a new inference kernel cannot arrive with whole-model goldens as its only test."""
+    import ast
+    exempt = lambda s: s.startswith("ullsam_set_") or s.startswith("ullsam_train_set_") or s in ("ullsam_last_error_string", "ullsam_abi_version", "ullsam_device_count")
+    names = [s for s in _header_symbols() if not s.startswith("ullsam_train_") and not exempt(s)]
+    assert len(names) >= 50
+    tree = ast.parse(open(os.path.join(ROOT, "ullsam_amd", "ops.py")).read())
+    wrappers = {}                                                   # symbol -> the ops functions whose bodies name it
+    for fn in tree.body:
+        if isinstance(fn, ast.FunctionDef):
+            for node in ast.walk(fn):
+                if isinstance(node, ast.Constant) and isinstance(node.value, str) and re.fullmatch(r"ullsam_[a-z0-9_]+", node.value):
+                    wrappers.setdefault(node.value, set()).add(fn.name)
+    here = os.path.join(ROOT, "tests")
+    text = "".join(open(os.path.join(here, f)).read() for f in sorted(os.listdir(here)) if f.startswith("test_") and f.endswith(".py"))
+    reached = lambda s: re.search(r"\b" + s + r"\b", text) or any(re.search(r"\bops\." + w + r"\(", text) for w in wrappers.get(s, ()))
+    missing = [s for s in names if not reached(s)]
+    assert not missing, f"inference entry points no test reaches: {missing}"

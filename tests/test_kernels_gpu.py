@@ -604,6 +604,13 @@ def test_vit_window_attention_row_group_kernel_against_the_block_kernel_and_floa
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("B,S,H,KVH,pad", [(2, 70, 2, 1, 9), (1, 200, 4, 2, 0), (1, 1081, 2, 2, 0)])
 def test_rope_and_causal_attention(ops, dtype, B, S, H, KVH, pad):
+    """RoPE + cache append, then causal prefill attention against the numpy oracle with the reference's literal additive masks.
+    Padded QUERY rows (left padding: every key such a row may see is padded) -- what the kernels guarantee, and why that is enough: the row is FINITE, a
+    convex combination of V rows.  It is not the reference's row: there every single-masked key weighs the same, the keys BEHIND the diagonal that are
+    not padded included (causal finfo.min alone), while the kernels do not form 32-key blocks that lie wholly behind a wave's last query.  Measured on
+    an MI355X at (B 2, S 70, pad 9): the padded rows are 0.535 (fp32) / 0.538 (bf16) away from the literal-mask reference, the valid rows 7.2e-7 / 7.6e-3.  The difference cannot reach a valid row: such a row only becomes a K / V
+    row at a padded position of the next layer, and a valid query gives a padded key the probability exp(finfo.min - max) = 0 exactly, so any finite
+    K / V there contributes 0 -- asserted here by replacing the padded K / V rows with other finite values: the valid rows keep their bits."""
     hd, G = 128, H // KVH
     rng = np.random.default_rng(S)
     qkv = rng.standard_normal((B, S, KVH, G + 2, hd), dtype=np.float32)
@@ -630,6 +637,17 @@ def test_rope_and_causal_attention(ops, dtype, B, S, H, KVH, pad):
     got = out.float().cpu().numpy().reshape(B, S, H * hd)
     valid = mask.astype(bool)
     assert err(got[valid], ref[valid]) < (2e-4 if dtype == torch.float32 else 4e-2)
+    assert np.isfinite(got).all()                                    # the padded query rows too
+    if pad:
+        print(f"causal attention {dtype} S={S} pad={pad}: padded query rows differ from the literal-mask reference by {err(got[~valid], ref[~valid]):.3e} "
+              f"(valid rows {err(got[valid], ref[valid]):.3e})")
+        assert np.abs(got[~valid]).max() <= np.abs(vc[-1].float().cpu().numpy()).max() * (1 + 1e-2)      # a convex combination of V rows
+        kc2, vc2 = kc.clone(), vc.clone()
+        kc2[-1, :, :pad] = kc2[-1, :, :pad] * -37.5 + 3.0            # other finite K / V rows at the padded positions
+        vc2[-1, :, :pad] = vc2[-1, :, :pad] * 100.0 - 5.0
+        out2 = ops.causal_attention(qo, kc2, vc2, T(mask.astype(np.int32), torch.int32), B, H, KVH, hd, S, S, 0)
+        vt = torch.from_numpy(valid.reshape(-1)).to(DEV)
+        assert torch.equal(out2[vt], out[vt]) and bool(torch.isfinite(out2.float()).all())
 
 
 @pytest.mark.parametrize("B,Sq,past,H,KVH,pad", [(4, 1081, 0, 32, 8, 13), (2, 70, 0, 2, 1, 9), (1, 200, 0, 4, 2, 0), (1, 129, 0, 2, 2, 0),
@@ -638,7 +656,10 @@ def test_causal_attention_dma_kernel_is_bit_identical_to_the_tiled_kernel(ops, B
     """causal128_attn_kernel (bf16, head_dim 128: K/V tiles by LDS-DMA into a double-buffered, XOR-swizzled LDS image) against the tiled
     flash_attn_kernel (attention variant 11) on the same operands: same MFMA order, same mask arithmetic, so the outputs must be equal bit for
     bit -- ragged query blocks, left padding, cached keys before the first query (q_pos0 > 0), a single query, the bench's shape -- and both
-    agree with a float64 softmax of the reference's additive finfo.min masks (modeling_internlm2.py:96-125)."""
+    agree with a float64 softmax of the reference's additive finfo.min masks (modeling_internlm2.py:96-125).
+    Padded query rows: finite in both kernels (and equal bit for bit between them), not the reference's rows, and without effect on any valid row --
+    the guarantee, the reason and the check are those of test_rope_and_causal_attention.  Measured on an MI355X: padded rows 0.40 (B 3, Sq 64, pad 5), 0.52
+    (B 2, Sq 70, pad 9), 0.75 (B 4, Sq 1081, pad 13) away from the literal-mask reference; valid rows 7.6e-3 ... 9.9e-3."""
     from ullsam_amd import _lib
     lib = _lib.load()
     hd, G, Sk = 128, H // KVH, past + Sq
@@ -670,6 +691,16 @@ def test_causal_attention_dma_kernel_is_bit_identical_to_the_tiled_kernel(ops, B
     ref = (torch.softmax((sc + add).float(), -1).double() @ vf).permute(0, 2, 1, 3).reshape(B * Sq, H * hd)
     valid = (mask[:, past:] != 0).reshape(-1)
     assert float((new.double() - ref)[valid].abs().max()) < 4e-2
+    assert bool(torch.isfinite(new.float()).all())                   # the padded query rows too
+    if pad and not bool(valid.all()):
+        print(f"causal128 B={B} Sq={Sq} past={past} pad={pad}: padded query rows differ from the literal-mask reference by "
+              f"{float((new.double() - ref)[~valid].abs().max()):.3e} (valid rows {float((new.double() - ref)[valid].abs().max()):.3e})")
+        assert float(new[~valid].float().abs().max()) <= float(vc[-1, :, :Sk].float().abs().max()) * (1 + 1e-2)     # a convex combination of V rows
+        kc2, vc2 = kc.clone(), vc.clone()
+        kc2[-1, :, :pad] = kc2[-1, :, :pad] * -37.5 + 3.0            # other finite K / V rows at the padded positions
+        vc2[-1, :, :pad] = vc2[-1, :, :pad] * 100.0 - 5.0
+        again = ops.causal_attention(q, kc2, vc2, km, B, H, KVH, hd, Sq, Sk, past)
+        assert torch.equal(again[valid], new[valid]) and bool(torch.isfinite(again.float()).all())
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

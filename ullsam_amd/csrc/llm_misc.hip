@@ -159,7 +159,7 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ 
     const float* row = x + (long)blockIdx.x * ld;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     float best = -INFINITY;
-    long long bi = 0x7fffffffffffffffLL;
+    long long bi = tid;   // the thread's first index: a row of nothing but -inf (or NaN, which `>` never takes) yields index 0 like torch.argmax, never an index outside [0, V)
     // four independent loads per trip; within a thread indices increase, so `>` keeps the first maximum
     for (long i0 = tid; i0 < V; i0 += 4096) {
         float v[4];
