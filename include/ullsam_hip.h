@@ -25,8 +25,10 @@ extern "C" {
 #define ULLSAM_ACT_RELU 2
 #define ULLSAM_ACT_SWIGLU 3 /* paired 64-column gate/up blocks -> silu(gate)*up */
 
-/* Bumped whenever an entry point is added or a signature changes.  The Python binding refuses a library that reports another
-   version (a stale libullsam_hip.so would otherwise receive shifted arguments, e.g. a row count where the stream is expected). */
+/* Bumped whenever the signature or the meaning of an EXISTING entry point changes.  The Python binding refuses a library that reports another
+   version (a stale libullsam_hip.so would otherwise receive shifted arguments, e.g. a row count where the stream is expected).  An entry point
+   that is only ADDED leaves the number alone (ullsam_sample_topk_topp did): a library built before it lacks the symbol, which the binding's
+   load reports by name, and the in-tree build's stamp covers this header and every source, so a stale library is rebuilt either way. */
 #define ULLSAM_ABI_VERSION 14
 
 const char* ullsam_last_error_string(void);
@@ -258,6 +260,24 @@ int ullsam_rope_split(int dtype, const void* qkv, void* q_out, void* k_cache, vo
                       int cache_pos0, int tab_rows, void* stream);                       /* modeling_internlm2.py:361-388,233-247;
                                                                                             pos is clamped to [0, tab_rows) */
 int ullsam_argmax(const float* logits, long long* out, int rows, long V, long ld, void* stream);
+/* One token per row from temperature / top-k / top-p sampling on fp32 logits [rows, V] (row stride ld >= V), the caption path's policy: app.py:469-477
+ * calls chat(do_sample=True, temperature=0.7, top_k=50, top_p=0.9), which reaches transformers' generate (modeling_internvl_sam.py:314 -> :433
+ * language_model.generate(**generate_kwargs)) and its TemperatureLogitsWarper / TopKLogitsWarper / TopPLogitsWarper + multinomial.  One launch; per row:
+ *   candidates  the min(top_k, V) largest logits (NaN counts as -inf), descending, equal values by ascending id -- ties at the k-th value go to the
+ *               lower ids, so exactly top_k tokens stay (transformers keeps every token tied with the k-th);
+ *   p_j         exp((x_j - x_0) / temperature) / sum, fp32;
+ *   nucleus     candidate j stays iff j == 0 or the mass strictly before it is < top_p (top_p >= 1: all stay); renormalised over those that stay;
+ *   u           u_in[row], or Philox4x32-10 with key (seeds[row] & 0xffffffff, seeds[row] >> 32) and counter (step & 0xffffffff, step >> 32, 0, 0):
+ *               u = (word 0 >> 8) * 2^-24 in [0, 1); written to u_out when that is not NULL;
+ *   draw        the first remaining candidate whose inclusive cumulative mass exceeds u * total, else the last one of non-zero probability.
+ * A row with a +inf yields the first +inf id, a row with nothing above -inf yields 0 (like ullsam_argmax), both with all mass on candidate 0; the result is
+ * always in [0, V).  cand_ids int64 / cand_p fp32 [rows, top_k] (NULL or both kinds independently): the ordered candidates and their final probabilities
+ * (0 for the removed ones; slots past min(top_k, V): -1 and 0).  The result is a pure function of (row, temperature, top_k, top_p, seed, step).
+ * < 0 for top_k outside 1..1024, temperature <= 0, top_p <= 0. */
+int ullsam_sample_topk_topp(const float* logits, long long* out, int rows, long V, long ld, float temperature, int top_k, float top_p,
+                            const unsigned long long* seeds /* [rows], device */, unsigned long long step,
+                            const float* u_in /* [rows] or NULL */, float* u_out /* [rows] or NULL */,
+                            long long* cand_ids /* [rows, top_k] or NULL */, float* cand_p /* [rows, top_k] or NULL */, void* stream);
 
 /* Prompt encoder / mask decoder */
 int ullsam_small_linear(const float* x, long ldx, const float* W, const float* b, const float* res, long ldr, float* y,

@@ -65,6 +65,7 @@ SIGNATURES = {
     "ullsam_gather_rows": [vp, vp, vp, i32, i32, i32, i32, vp],
     "ullsam_rope_split": [i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "ullsam_argmax": [vp, vp, i32, i64, i64, vp],
+    "ullsam_sample_topk_topp": [vp, vp, i32, i64, i64, f32, i32, f32, vp, C.c_ulonglong, vp, vp, vp, vp, vp],
     "ullsam_small_linear": [vp, i64, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp],
     "ullsam_i2t_block": [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, i64, vp, vp, vp, i32, i32, i32, f32, vp],
     "ullsam_kv_proj": [vp, vp, vp, vp, vp, vp, vp, vp, i64, vp],

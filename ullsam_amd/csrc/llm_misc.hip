@@ -190,3 +190,230 @@ extern "C" int ullsam_argmax(const float* logits, long long* out, int rows, long
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
+
+// ---- seeded top-k / top-p sampling on fp32 logits [R, V] -> int64 (app.py:469-477: chat(do_sample, T 0.7, top_k 50, top_p 0.9)) ----
+// One 1024-thread workgroup per row:
+//   1. V > 1024: the smallest of the 1024 threads' maxima is a floor -- at least 1024 >= top_k values lie at or above it, so nothing below it is a
+//      candidate and the histograms below count only what is left (a few percent of an ordinary row);
+//   2. radix select of the k-th largest order-preserving key, 8 bits a pass (integer LDS histogram), ended as soon as everything at or above the
+//      selected bin fits the 1024 sort slots;
+//   3. those values into the slots (key << 32 | ~id), bitonic sort descending = (value descending, id ascending): the first min(top_k, V) are the
+//      candidates.  Only when more than 1024 values would remain after all four passes (ties at the k-th value) are the tied ones taken in id order
+//      by a scan over contiguous per-thread ranges;
+//   4. wave 0: softmax over the candidates, nucleus prefix, draw.
+// Integer atomics only and a total order in the sort: the result is a pure function of (row, T, k, p, seed, step).
+__device__ __forceinline__ unsigned int sample_key(float x) {   // larger value <=> larger key; NaN -> -inf, -0 -> +0 (equal values, equal keys)
+    unsigned int b = __float_as_uint(x);
+    if ((b & 0x7fffffffu) > 0x7f800000u) b = 0xff800000u;
+    if ((b << 1) == 0u) b = 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float sample_value(unsigned int k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// Philox4x32-10 (Salmon et al., SC'11; Random123), word 0 of the block with counter (step lo, step hi, 0, 0) and key (seed lo, seed hi)
+__device__ __forceinline__ unsigned int philox4x32_10_word0(unsigned long long seed, unsigned long long step) {
+    unsigned int c0 = (unsigned int)step, c1 = (unsigned int)(step >> 32), c2 = 0u, c3 = 0u;
+    unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned int h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const unsigned int h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+template <typename T> __device__ __forceinline__ T wave_scan_incl(T v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T t = __shfl_up(v, o, 64);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+
+#define SAMPLE_CAP 1024
+__global__ __launch_bounds__(1024) void sample_topk_topp_kernel(const float* __restrict__ x, long long* __restrict__ out, long V, long ld, float temperature,
+                                                                int top_k, float top_p, const unsigned long long* __restrict__ seeds, unsigned long long step,
+                                                                const float* __restrict__ u_in, float* __restrict__ u_out, long long* __restrict__ cand_ids,
+                                                                float* __restrict__ cand_p) {
+    __shared__ unsigned long long cand[SAMPLE_CAP];   // key << 32 | (2^32 - 1 - id); 0 = empty (below every key: -inf's is 0x007fffff)
+    __shared__ float sp[SAMPLE_CAP];
+    __shared__ int hist[256];
+    __shared__ unsigned int wred[16];
+    __shared__ int s_above, s_inbin, s_digit, s_n;
+    __shared__ float s_total;
+    const long r = blockIdx.x;
+    const float* row = x + r * ld;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int kk = (int)min((long)top_k, V);
+    cand[tid] = 0ull;
+    if (tid == 0) s_n = 0;
+    unsigned int prefix = 0u, mask = 0u, floor_key = 0u;
+    int above = 0, inbin = (int)min(V, (long)SAMPLE_CAP);
+    if (V > SAMPLE_CAP) {
+        unsigned int tmax = 0u;
+        for (long i0 = tid; i0 < V; i0 += 4096) {
+            float v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = (i0 + 1024 * u < V) ? row[i0 + 1024 * u] : -INFINITY;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) tmax = max(tmax, sample_key(v[u]));   // (a slot past V counts as -inf, the smallest key: it never raises a maximum)
+        }
+        for (int o = 32; o > 0; o >>= 1) tmax = min(tmax, (unsigned int)__shfl_xor(tmax, o, 64));
+        if (lane == 0) wred[wv] = tmax;
+        __syncthreads();
+        floor_key = wred[0];
+        for (int w = 1; w < 16; ++w) floor_key = min(floor_key, wred[w]);
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) hist[tid] = 0;
+            __syncthreads();
+            for (long i0 = tid; i0 < V; i0 += 4096) {
+                float v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] = (i0 + 1024 * u < V) ? row[i0 + 1024 * u] : 0.f;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const unsigned int k = sample_key(v[u]);
+                    if (i0 + 1024 * u < V && k >= floor_key && (k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1);
+                }
+            }
+            __syncthreads();
+            if (wv == 0) {   // bins from the top: lane l owns 255 - 4l .. 252 - 4l; the bin in which the count from above reaches kk
+                int h[4], s = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { h[j] = hist[255 - 4 * lane - j]; s += h[j]; }
+                int a = above + wave_scan_incl(s, lane) - s;
+                if (a < kk && kk <= a + s) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (a < kk && kk <= a + h[j]) { s_above = a; s_inbin = h[j]; s_digit = 255 - 4 * lane - j; }
+                        a += h[j];
+                    }
+                }
+            }
+            __syncthreads();
+            above = s_above; inbin = s_inbin;
+            prefix |= (unsigned int)s_digit << shift;
+            mask |= 255u << shift;
+            if (above + inbin <= SAMPLE_CAP) break;
+        }
+    } else {
+        __syncthreads();
+    }
+    // more than the slots hold at or above the k-th key after all 32 bits: the surplus are values EQUAL to the k-th (above < kk <= 1024)
+    const bool tied = above + inbin > SAMPLE_CAP;
+    for (long i0 = tid; i0 < V; i0 += 4096) {
+        float v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = (i0 + 1024 * u < V) ? row[i0 + 1024 * u] : 0.f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const long i = i0 + 1024 * u;
+            const unsigned int k = sample_key(v[u]);
+            if (i < V && (tied ? k > prefix : (k >= floor_key && (k & mask) >= prefix))) {
+                const int slot = atomicAdd(&s_n, 1);
+                if (slot < SAMPLE_CAP) cand[slot] = ((unsigned long long)k << 32) | (0xffffffffu - (unsigned int)i);
+            }
+        }
+    }
+    __syncthreads();
+    int n = min(s_n, SAMPLE_CAP);
+    if (tied) {   // the kk - above lowest ids among the values equal to the k-th: thread t scans ids [t C, (t + 1) C), ranks by an exclusive scan of the threads' counts
+        const int need = kk - above;
+        const long C = (V + 1023) / 1024, lo = min(V, tid * C), hi = min(V, lo + C);
+        int cnt = 0;
+        for (long i = lo; i < hi && cnt < need; ++i) cnt += sample_key(row[i]) == prefix;   // (clamped at need: ranks below need are exact, later threads see >= need)
+        const int incl = wave_scan_incl(cnt, lane);
+        if (lane == 63) hist[wv] = incl;
+        __syncthreads();
+        int rank = incl - cnt;
+        for (int w = 0; w < wv; ++w) rank += hist[w];
+        for (long i = lo; i < hi && rank < need; ++i)
+            if (sample_key(row[i]) == prefix) { cand[above + rank] = ((unsigned long long)prefix << 32) | (0xffffffffu - (unsigned int)i); ++rank; }
+        n = kk;
+        __syncthreads();
+    }
+    int P = 64;
+    while (P < n) P <<= 1;
+    for (int k2 = 2; k2 <= P; k2 <<= 1)
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            const int p = tid ^ j;
+            if (tid < P && p > tid) {
+                const unsigned long long a = cand[tid], b = cand[p];
+                if (((tid & k2) == 0) ? a < b : a > b) { cand[tid] = b; cand[p] = a; }
+            }
+            __syncthreads();
+        }
+    if (wv == 0) {   // ---- wave 0: lane l owns candidates [l C, (l + 1) C), and reads back only the sp[] slots it wrote ----
+        const int C = (kk + 63) / 64, j0 = min(kk, lane * C), j1 = min(kk, j0 + C);
+        const float x0 = sample_value((unsigned int)(cand[0] >> 32));
+        const bool degenerate = x0 == INFINITY || x0 == -INFINITY;   // a +inf (the first one leads the order) or nothing above -inf (id 0 leads): all mass on candidate 0
+        float u;
+        if (u_in) u = u_in[r];
+        else u = (float)(philox4x32_10_word0(seeds[r], step) >> 8) * 5.9604644775390625e-8f;   // 2^-24: [0, 1)
+        if (lane == 0 && u_out) u_out[r] = u;
+        float ls = 0.f;
+        for (int j = j0; j < j1; ++j) {
+            const float e = degenerate ? (j == 0 ? 1.f : 0.f) : expf((sample_value((unsigned int)(cand[j] >> 32)) - x0) / temperature);
+            sp[j] = e;
+            ls += e;
+        }
+        const float sum = wave_sum(ls);
+        float lp = 0.f;
+        for (int j = j0; j < j1; ++j) { const float p = sp[j] / sum; sp[j] = p; lp += p; }
+        // nucleus: candidate j stays iff j == 0 or the mass before it is below top_p; the kept set is the prefix in front of the first one that goes
+        float m = wave_scan_incl(lp, lane) - lp;
+        int first_out = kk;
+        for (int j = j0; j < j1; ++j) {
+            if (first_out == kk && j != 0 && top_p < 1.f && !(m < top_p)) first_out = j;
+            m += sp[j];
+        }
+        for (int o = 32; o > 0; o >>= 1) first_out = min(first_out, __shfl_xor(first_out, o, 64));
+        const int K = first_out;
+        float lt = 0.f;
+        for (int j = j0; j < min(j1, K); ++j) lt += sp[j];
+        const float incl = wave_scan_incl(lt, lane);
+        const float total = __shfl(incl, 63, 64);
+        // draw: the first kept candidate (of non-zero probability) whose inclusive mass exceeds u * total, else the last such candidate
+        const float target = u * total;
+        float c = incl - lt;
+        int pick = kk, last = 0;
+        for (int j = j0; j < min(j1, K); ++j) {
+            c += sp[j];
+            if (sp[j] > 0.f) {
+                last = j;
+                if (pick == kk && c > target) pick = j;
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            pick = min(pick, __shfl_xor(pick, o, 64));
+            last = max(last, __shfl_xor(last, o, 64));
+        }
+        if (pick == kk) pick = last;
+        if (lane == 0) { out[r] = (long long)(0xffffffffu - (unsigned int)cand[pick]); s_above = K; s_total = total; }
+    }
+    __syncthreads();
+    const int K = s_above;
+    const float total = s_total;
+    if (cand_ids)
+        for (int j = tid; j < top_k; j += 1024) cand_ids[r * top_k + j] = j < kk ? (long long)(0xffffffffu - (unsigned int)cand[j]) : -1ll;
+    if (cand_p)
+        for (int j = tid; j < top_k; j += 1024) cand_p[r * top_k + j] = j < K ? sp[j] / total : 0.f;
+}
+
+extern "C" int ullsam_sample_topk_topp(const float* logits, long long* out, int rows, long V, long ld, float temperature, int top_k, float top_p,
+                                       const unsigned long long* seeds, unsigned long long step, const float* u_in, float* u_out,
+                                       long long* cand_ids, float* cand_p, void* stream) {
+    ULLSAM_CHECK(top_k >= 1 && top_k <= SAMPLE_CAP, "sample_topk_topp: top_k %d outside 1..%d", top_k, SAMPLE_CAP);
+    ULLSAM_CHECK(temperature > 0.f, "sample_topk_topp: temperature must be > 0");
+    ULLSAM_CHECK(top_p > 0.f, "sample_topk_topp: top_p must be > 0");
+    ULLSAM_CHECK(rows >= 0 && V >= 1 && V <= 0x7fffffffL && ld >= V, "sample_topk_topp: rows %d, V %ld, ld %ld", rows, V, ld);
+    ULLSAM_CHECK(seeds || u_in, "sample_topk_topp: neither seeds nor u_in");
+    if (rows == 0) return 0;
+    sample_topk_topp_kernel<<<rows, 1024, 0, reinterpret_cast<hipStream_t>(stream)>>>(logits, out, V, ld, temperature, top_k, top_p, seeds, step, u_in, u_out,
+                                                                                       cand_ids, cand_p);
+    ULLSAM_LAUNCH_CHECK();
+    return 0;
+}

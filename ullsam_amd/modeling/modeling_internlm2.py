@@ -20,6 +20,7 @@ from torch import nn
 
 from .. import ops
 from ..packing import pack_w13
+from ..sampling import row_seeds
 from .common import Linear, Packed
 from .configuration_internlm2 import InternLM2Config
 from .outputs import BaseModelOutputWithPast, CausalLMOutputWithPast
@@ -352,11 +353,15 @@ class InternLM2ForCausalLM(Packed):
     @torch.no_grad()
     def generate(self, input_ids=None, inputs_embeds=None, attention_mask=None, generation_config=None, max_new_tokens=None,
                  do_sample=False, eos_token_id=None, pad_token_id=None, temperature=1.0, top_k=None, top_p=None,
-                 use_cache=True, output_hidden_states=None, num_beams=1, **kwargs) -> torch.LongTensor:
+                 use_cache=True, output_hidden_states=None, num_beams=1, seed=None, **kwargs) -> torch.LongTensor:
         """Token loop with the reference's prepare_inputs_for_generation semantics (:1112-1149): the first step consumes
         inputs_embeds (or input_ids), later steps the last id with position_ids = cumsum(mask)-1.  Returns only the new tokens
         when inputs_embeds is given, prompt + new tokens when input_ids is given (HF GenerationMixin behaviour).
-        Greedy by default (bit-exact parity path); do_sample applies temperature / top-k / top-p on the fp32 logits."""
+        Greedy by default (bit-exact parity path); do_sample applies temperature / top-k / top-p on the fp32 logits.
+        seed (an int: sequence b draws with seed + b; or one int per sequence), with do_sample: every step's token comes from ONE kernel
+        (ops.sample_topk_topp) whose uniform is Philox(seed of the sequence, step) -- a sequence's draws depend on nothing but its seed and its logits,
+        so a caption is reproduced whatever the batch it ran in and whatever used the global torch generator, which is left alone; top_k must be 1..1024.
+        Without seed, sampling is torch.multinomial on the global generator, as before."""
         if num_beams != 1:
             raise NotImplementedError("beam search is not part of the uLLSAM hot path")
         if generation_config is not None:
@@ -364,6 +369,7 @@ class InternLM2ForCausalLM(Packed):
             max_new_tokens = max_new_tokens or g.get("max_new_tokens")
             eos_token_id = eos_token_id if eos_token_id is not None else g.get("eos_token_id")
             do_sample = do_sample or bool(g.get("do_sample", False))
+            seed = seed if seed is not None else g.get("seed")
         max_new_tokens = int(max_new_tokens or 20)
         eos = eos_token_id if eos_token_id is not None else self.config.eos_token_id
         eos_set = set(eos) if isinstance(eos, (list, tuple)) else {int(eos)}
@@ -387,9 +393,15 @@ class InternLM2ForCausalLM(Packed):
         # `eos_check_every` steps earlier (pinned buffer + event, no stream sync): the host keeps enqueueing steps while the GPU works,
         # and at most that many surplus steps run after the last eos; their tokens are `pad` and are trimmed below, so the returned
         # ids are exactly those of a loop that tests every step.
-        # With do_sample the test is made every step (blocking): a surplus step would draw from the global torch RNG and leave its state
+        # With do_sample and no seed the test is made every step (blocking): a surplus step would draw from the global torch RNG and leave its state
         # different from a loop that stops at once, so later sampled calls would not reproduce against the reference loop.
-        every = 0 if do_sample else max(1, int(kwargs.get("eos_check_every", 8)))
+        # With a seed the draws are a function of (seed, step) alone: surplus steps change nothing, and the sampled loop pipelines its test like greedy.
+        fused = bool(do_sample) and seed is not None
+        if fused:
+            if top_k is None or not 1 <= int(top_k) <= 1024:
+                raise ValueError(f"generate(seed=...) samples with the fused kernel, which needs top_k in 1..1024 (got {top_k})")
+            seeds_t = torch.from_numpy(row_seeds(seed, B).view("int64")).to(dev)
+        every = 0 if do_sample and not fused else max(1, int(kwargs.get("eos_check_every", 8)))
         flags = torch.empty((max_new_tokens,), dtype=torch.bool, pin_memory=True) if track_eos else None  # one pinned buffer per call
         pending = []  # (step index, event)
         stop_at = None
@@ -398,7 +410,9 @@ class InternLM2ForCausalLM(Packed):
         pos_next = mask.sum(-1, keepdim=True).to(torch.int32)  # = cumsum(mask)[:, -1]: position id of the next token (cumsum - 1 of the extended mask)
         for step in range(max_new_tokens):
             logits = self.lm_head(h_last, prefill=step == 0 and S > 1)  # fp32 [B, V], last position only
-            if do_sample:
+            if fused:
+                tok = ops.sample_topk_topp(logits.contiguous(), max(float(temperature or 1.0), 1e-5), int(top_k), float(top_p or 1.0), seeds_t, step)
+            elif do_sample:
                 tok = _sample(logits, temperature, top_k, top_p)
             else:
                 tok = ops.argmax(logits.contiguous())

@@ -601,6 +601,30 @@ def argmax(logits: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def sample_topk_topp(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, seeds: torch.Tensor, step: int,
+                     u: Optional[torch.Tensor] = None, return_debug: bool = False):
+    """One token id per row of fp32 logits [R, V] by temperature / top-k / top-p sampling in one launch (ullsam_sample_topk_topp in the header has the
+    definition).  seeds: int64 [R] on the device, read as unsigned 64-bit Philox keys (sampling.row_seeds); step: the Philox counter; u: fp32 [R] uniforms
+    that replace the generator's.  return_debug: also (u used, candidate ids [R, top_k], their final probabilities [R, top_k])."""
+    _chk(logits, "logits", torch.float32); _chk(seeds, "seeds", torch.int64)
+    assert logits.dim() == 2, "logits must be [rows, V]"
+    R, V = logits.shape
+    assert seeds.numel() == R and seeds.device == logits.device
+    if u is not None:
+        _chk(u, "u", torch.float32)
+        assert u.numel() == R and u.device == logits.device
+    dev = logits.device
+    out = torch.empty((R,), dtype=torch.int64, device=dev)
+    u_out = cand_ids = cand_p = None
+    if return_debug:
+        u_out = torch.empty((R,), dtype=torch.float32, device=dev)
+        cand_ids = torch.empty((R, max(int(top_k), 0)), dtype=torch.int64, device=dev)
+        cand_p = torch.empty((R, max(int(top_k), 0)), dtype=torch.float32, device=dev)
+    _lib.call("ullsam_sample_topk_topp", logits.data_ptr(), out.data_ptr(), R, V, V, float(temperature), int(top_k), float(top_p), seeds.data_ptr(),
+              int(step) & 0xFFFFFFFFFFFFFFFF, _p(u), _p(u_out), _p(cand_ids), _p(cand_p), _stream())
+    return (out, u_out, cand_ids, cand_p) if return_debug else out
+
+
 def small_linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], act: int = ACT_NONE,
                  res: Optional[torch.Tensor] = None) -> torch.Tensor:
     _chk(x, "x", torch.float32); _chk(w, "w", torch.float32)
