@@ -366,6 +366,30 @@ int ullsam_label_regions(const unsigned char* masks, long N, int H, int W, int b
                          void* stream);                                   /* amg.py:276 (cv2.connectedComponentsWithStats(.., 8)) */
 int ullsam_remove_small_regions(const unsigned char* masks_in, unsigned char* masks_out, long N, int H, int W, int area_thresh, int mode,
                                 void* workspace, long workspace_bytes, unsigned char* changed, void* stream);   /* amg.py:267-291 */
+/* Instance label maps: the records of one frame painted into ONE label image, and the contingency table two label images are scored from
+   (csrc/labels.hip; integer work, bit-exact with utils.amg's host forms).  N <= 65535, H * W < 2^31.
+   rle_paint_labels: counts / offsets as rle_to_mask; rank i32 [N] = the paint order (a permutation of 0..N-1, larger = on top).
+     raw i32 [W, H] -- TRANSPOSED, raw[x * H + y] -- is zero-filled, then = 1 + the largest rank among the records covering the pixel
+     (the app's sequential overwrite).  status i32 [N] = 1 where a count is negative, the counts do not sum to H * W or the rank is outside
+     0..N-1; no store leaves the frame and no label exceeds N.
+   label_stats: areas i32 [N + 1], boxes i32 [N + 1, 4] (x0, y0, x1, y1 inclusive) of the pixels carrying each RAW label (entry 0 unused;
+     a label that is not visible keeps area 0 and the box INT_MAX, INT_MAX, -1, -1).
+   label_compact: a raw label is dropped when its visible area is 0 or < min_visible_area; the others are renumbered 1..K in paint order.
+     map i32 [N + 1] (raw -> final label, 0 = dropped), label_of_record i32 [N], areas i32 [N] / boxes i32 [N, 4] (first K entries), K i32 [1].
+   label_remap: labels i32 [H, W] (row-major) = map[raw[x * H + y]].
+   label_overlap: a, b i32 [H, W] with ids in 0..na / 0..nb -> T u64 [na + 1, nb + 1], T[i, j] = #{p : a[p] = i and b[p] = j} (zeroed here);
+     status i32 [1] = 1 when an id lies outside its range (that pixel is skipped).  (na + 1) * (nb + 1) <= 2^26.
+   resize_nearest_i32: in i32 [IH, IW] (row stride in_ld) resized to a virtual [OH, OW] by src = min(((2 dst + 1) * in) / (2 * out), in - 1)
+     per axis (Image.NEAREST); the window (top, left, h, w) of it is written to out (row stride out_ld). */
+int ullsam_rle_paint_labels(const int* counts, const long* offsets, const int* rank, long N, int H, int W, int* raw, int* status,
+                            void* stream);                                                    /* app.py:688-707 */
+int ullsam_label_stats(const int* raw, long N, int H, int W, int* areas, int* boxes, void* stream);
+int ullsam_label_compact(const int* areas_raw, const int* boxes_raw, const int* rank, long N, int min_visible_area, int* map,
+                         int* label_of_record, int* areas, int* boxes, int* K, void* stream);
+int ullsam_label_remap(const int* raw, const int* map, long N, int H, int W, int* labels, void* stream);   /* app.py:707 */
+int ullsam_label_overlap(const int* a, const int* b, int H, int W, int na, int nb, unsigned long long* T, int* status, void* stream);
+int ullsam_resize_nearest_i32(const int* in, long in_ld, int IH, int IW, int OH, int OW, int top, int left, int h, int w, int* out,
+                              long out_ld, void* stream);                                     /* app.py:807-826, 145 reverse_padding */
 
 /* fp8 (OCP e4m3) ViT path -- BASELINE.json configs[4]; the reference's bf16 encoder linears image_encoder.py:227,171-181 with
    8-bit operands: rows quantised with a per-row scale (optionally behind the block's LayerNorm :166,180), GEMM on the

@@ -92,6 +92,12 @@ SIGNATURES = {
     "ullsam_rle_to_mask": [vp, vp, i64, i32, i32, vp, vp, vp],
     "ullsam_label_regions": [vp, i64, i32, i32, i32, vp, vp],
     "ullsam_remove_small_regions": [vp, vp, i64, i32, i32, i32, i32, vp, i64, vp, vp],
+    "ullsam_rle_paint_labels": [vp, vp, vp, i64, i32, i32, vp, vp, vp],
+    "ullsam_label_stats": [vp, i64, i32, i32, vp, vp, vp],
+    "ullsam_label_compact": [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp],
+    "ullsam_label_remap": [vp, vp, i64, i32, i32, vp, vp],
+    "ullsam_label_overlap": [vp, vp, i32, i32, i32, i32, vp, vp, vp],
+    "ullsam_resize_nearest_i32": [vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp],
     "ullsam_rows_fp8": [vp, i32, i64, vp, i64, vp, vp, vp, i64, i32, f32, vp],
     "ullsam_gemm_fp8": [vp, i64, vp, vp, i64, vp, vp, i64, i32, vp, vp, i64, i32, i32, i32, i32, vp],
     "ullsam_rows_fp8_pow2": [vp, i32, i64, vp, i64, vp, i64, i32, vp],

@@ -346,9 +346,8 @@ class SamAutomaticMaskGenerator:
         mine = [self.generate(images[i]) for i in range(a, b)]
         return parallel.gather_sharded_lists(mine, len(images), group)
 
-    @torch.no_grad()
-    def generate(self, image) -> List[Dict[str, Any]]:
-        """image: HxWx3 uint8 / float array (0..255) or a [3,H,W] tensor.  Returns SAM-style records sorted as generated."""
+    def _generate_data(self, image):
+        """The generator up to the host copy of the surviving records' fields: (MaskData, (H, W))."""
         dev = self.model.device
         if isinstance(image, np.ndarray):
             image = torch.from_numpy(np.ascontiguousarray(image)).permute(2, 0, 1)
@@ -368,12 +367,41 @@ class SamAutomaticMaskGenerator:
                 data["rles"] = list(data["rles"])
             data = self.postprocess_small_regions(data, self.min_mask_region_area, max(self.box_nms_thresh, self.crop_nms_thresh))
         data.to_numpy()
+        return data, orig_size
+
+    @staticmethod
+    def _records(data: A.MaskData, output_mode: str) -> List[Dict[str, Any]]:
         out = []
         for i, rle in enumerate(data["rles"]):
             if not isinstance(rle["counts"], list):
                 rle = {"size": rle["size"], "counts": rle["counts"].tolist()}
-            seg = A.rle_to_mask(rle) if self.output_mode == "binary_mask" else (A.coco_encode_rle(rle) if self.output_mode == "coco_rle" else rle)
+            seg = A.rle_to_mask(rle) if output_mode == "binary_mask" else (A.coco_encode_rle(rle) if output_mode == "coco_rle" else rle)
             out.append({"segmentation": seg, "area": A.area_from_rle(rle), "bbox": A.box_xyxy_to_xywh(data["boxes"][i]).tolist(),
                         "predicted_iou": float(data["iou_preds"][i]), "point_coords": [data["points"][i].tolist()],
                         "stability_score": float(data["stability_score"][i]), "crop_box": A.box_xyxy_to_xywh(data["crop_boxes"][i]).tolist()})
         return out
+
+    @torch.no_grad()
+    def generate(self, image) -> List[Dict[str, Any]]:
+        """image: HxWx3 uint8 / float array (0..255) or a [3,H,W] tensor.  Returns SAM-style records sorted as generated."""
+        return self._records(self._generate_data(image)[0], self.output_mode)
+
+    @torch.no_grad()
+    def generate_label_map(self, image, order: str = "area", min_visible_area: int = 0, out_hw=None, window=None):
+        """Segment everything, then paint the records into ONE instance label image -- the file the app exports (app.py:688-707 save_instance,
+        :807-826 export_mask) -- on the device (utils.amg.paint_label_map; csrc/labels.hip).  -> (labels int32 [H, W] on the model's device,
+        records): the records are those of generate() with output_mode="uncompressed_rle", in the same order, each with one more key "label" = its
+        id in `labels` (0: the record is fully covered by records painted after it, or keeps fewer than `min_visible_area` visible pixels).
+        order: "area" (default; large first, so small objects stay on top), "score" (ascending predicted_iou) or "record" (list order, the app's).
+        out_hw / window = (top, left, h, w): nearest resize of the label image and the part of it to return (the app's export resize and
+        reverse_padding; utils.amg.resize_labels_nearest)."""
+        data, orig_size = self._generate_data(image)
+        records = self._records(data, "uncompressed_rle")
+        keys = [r["predicted_iou"] for r in records] if order == "score" else None
+        labels, of_record, _, _ = A.paint_label_map([r["segmentation"] for r in records], order=order, keys=keys, min_visible_area=min_visible_area,
+                                                    device=self.model.device, size=orig_size)
+        for r, l in zip(records, of_record.cpu().tolist()):
+            r["label"] = int(l)
+        if out_hw is not None or window is not None:
+            labels = A.resize_labels_nearest(labels, tuple(labels.shape) if out_hw is None else out_hw, window)
+        return labels, records

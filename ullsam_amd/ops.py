@@ -791,3 +791,97 @@ def remove_small_regions(masks: torch.Tensor, area_thresh: int, mode: str, out: 
     _lib.call("ullsam_remove_small_regions", masks.data_ptr(), out.data_ptr(), n, h, w, int(area_thresh), REGION_MODES[mode], ws.data_ptr(),
               ws.numel(), changed.data_ptr(), _stream())
     return out, changed, ws[:n * h * w * 4].view(torch.int32).view(n, h, w)
+
+
+# ---- instance label maps and their contingency table (csrc/labels.hip) ---------------------------------------------------------
+LABEL_MAX_RECORDS = 65535
+OVERLAP_MAX_CELLS = 1 << 26
+
+
+def _out_i32(out: Optional[torch.Tensor], shape, device, name: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=torch.int32, device=device)
+    _chk(out, name, torch.int32)
+    assert tuple(out.shape) == tuple(shape), (name, tuple(out.shape), tuple(shape))
+    return out
+
+
+def rle_paint_labels(counts: torch.Tensor, offsets: torch.Tensor, rank: torch.Tensor, h: int, w: int, out: Optional[torch.Tensor] = None,
+                     status: Optional[torch.Tensor] = None):
+    """Uncompressed column-major RLEs of one [h, w] frame (counts int32 concatenated, offsets int64 [N + 1]) and their paint ranks (int32 [N],
+    a permutation of 0..N-1, larger = on top) -> (raw int32 [w, h] -- TRANSPOSED -- = 1 + the largest rank covering the pixel, 0 where none does;
+    status int32 [N] = 1 for a record whose counts are negative / do not sum to h * w or whose rank is out of range: the caller reads it)."""
+    _chk(counts, "counts", torch.int32); _chk(offsets, "offsets", torch.int64); _chk(rank, "rank", torch.int32)
+    n = offsets.numel() - 1
+    assert 0 <= n <= LABEL_MAX_RECORDS and rank.numel() == n and h > 0 and w > 0
+    out = _out_i32(out, (w, h), counts.device, "out")
+    status = _out_i32(status, (n,), counts.device, "status")
+    _lib.call("ullsam_rle_paint_labels", counts.data_ptr(), offsets.data_ptr(), rank.data_ptr(), n, h, w, out.data_ptr(), status.data_ptr(), _stream())
+    return out, status
+
+
+def label_stats(raw: torch.Tensor, n: int):
+    """raw int32 [w, h] (transposed, labels 0..n) -> (areas int32 [n + 1], boxes int32 [n + 1, 4] inclusive XYXY) per RAW label; a label that is not
+    visible has area 0 and the box (INT_MAX, INT_MAX, -1, -1)."""
+    _chk(raw, "raw", torch.int32)
+    w, h = raw.shape
+    areas = torch.empty((n + 1,), dtype=torch.int32, device=raw.device)
+    boxes = torch.empty((n + 1, 4), dtype=torch.int32, device=raw.device)
+    _lib.call("ullsam_label_stats", raw.data_ptr(), n, h, w, areas.data_ptr(), boxes.data_ptr(), _stream())
+    return areas, boxes
+
+
+def label_compact(areas_raw: torch.Tensor, boxes_raw: torch.Tensor, rank: torch.Tensor, min_visible_area: int = 0, k_out: Optional[torch.Tensor] = None):
+    """Drop the raw labels whose visible area is 0 or < min_visible_area and renumber the others 1..K in paint order -> (map int32 [N + 1]: raw -> final
+    label, label_of_record int32 [N], areas int32 [N], boxes int32 [N, 4] -- their first K entries hold the final labels' -- and K int32 [1])."""
+    _chk(areas_raw, "areas_raw", torch.int32); _chk(boxes_raw, "boxes_raw", torch.int32); _chk(rank, "rank", torch.int32)
+    n = rank.numel()
+    assert areas_raw.numel() == n + 1 and boxes_raw.numel() == 4 * (n + 1)
+    dev = rank.device
+    lmap = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+    of_record = torch.empty((n,), dtype=torch.int32, device=dev)
+    areas = torch.zeros((n,), dtype=torch.int32, device=dev)
+    boxes = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+    k_out = _out_i32(k_out, (1,), dev, "k_out")
+    _lib.call("ullsam_label_compact", areas_raw.data_ptr(), boxes_raw.data_ptr(), rank.data_ptr(), n, int(min_visible_area), lmap.data_ptr(),
+              of_record.data_ptr(), areas.data_ptr(), boxes.data_ptr(), k_out.data_ptr(), _stream())
+    return lmap, of_record, areas, boxes, k_out
+
+
+def label_remap(raw: torch.Tensor, lmap: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """raw int32 [w, h] (transposed), lmap int32 [N + 1] -> labels int32 [h, w] = lmap[raw[x, y]]."""
+    _chk(raw, "raw", torch.int32); _chk(lmap, "lmap", torch.int32)
+    w, h = raw.shape
+    out = _out_i32(out, (h, w), raw.device, "out")
+    _lib.call("ullsam_label_remap", raw.data_ptr(), lmap.data_ptr(), lmap.numel() - 1, h, w, out.data_ptr(), _stream())
+    return out
+
+
+def label_overlap(a: torch.Tensor, b: torch.Tensor, na: int, nb: int):
+    """Label images a, b int32 [h, w] with ids in 0..na / 0..nb -> (T int64 [na + 1, nb + 1], T[i, j] = #{p: a[p] = i and b[p] = j}; status int32 [1] = 1
+    when some id lies outside its range -- that pixel is skipped; the caller reads it)."""
+    _chk(a, "a", torch.int32); _chk(b, "b", torch.int32)
+    assert a.dim() == 2 and a.shape == b.shape, (a.shape, b.shape)
+    na, nb = int(na), int(nb)
+    if na < 0 or nb < 0 or (na + 1) * (nb + 1) > OVERLAP_MAX_CELLS:
+        raise _lib.UllsamError(f"label_overlap: the table [{na + 1}, {nb + 1}] must have between 1 and 2^26 cells")
+    h, w = a.shape
+    table = torch.empty((na + 1, nb + 1), dtype=torch.int64, device=a.device)
+    status = torch.empty((1,), dtype=torch.int32, device=a.device)
+    _lib.call("ullsam_label_overlap", a.data_ptr(), b.data_ptr(), h, w, na, nb, table.data_ptr(), status.data_ptr(), _stream())
+    return table, status
+
+
+def resize_nearest_i32(x: torch.Tensor, out_hw, window=None) -> torch.Tensor:
+    """Nearest resize of an int32 image [ih, iw] to [oh, ow] by src = min(((2 dst + 1) * in) // (2 * out), in - 1) per axis (PIL's Image.NEAREST,
+    torch's nearest-exact); window = (top, left, h, w) returns only that part of the resized image."""
+    _chk(x, "x", torch.int32)
+    assert x.dim() == 2
+    ih, iw = x.shape
+    oh, ow = (int(v) for v in out_hw)
+    top, left, h, w = (0, 0, oh, ow) if window is None else (int(v) for v in window)
+    if not (ih > 0 and iw > 0 and oh > 0 and ow > 0 and top >= 0 and left >= 0 and h >= 0 and w >= 0 and top + h <= oh and left + w <= ow):
+        raise _lib.UllsamError(f"resize_nearest_i32: window {(top, left, h, w)} does not lie inside the resized image {(oh, ow)}")
+    out = torch.empty((h, w), dtype=torch.int32, device=x.device)
+    _lib.call("ullsam_resize_nearest_i32", x.data_ptr(), iw, ih, iw, oh, ow, top, left, h, w, out.data_ptr(), w, _stream())
+    return out

@@ -425,17 +425,23 @@ def batched_nms(boxes: torch.Tensor, scores: torch.Tensor, idxs: torch.Tensor, i
 
 
 # ---- connected regions on the device (csrc/regions.hip) ---------------------------------------------------------------------
-def _rle_expand(rles: Sequence[Dict[str, Any]], device) -> Tuple[torch.Tensor, torch.Tensor]:
-    """RLE dicts of ONE frame size -> (masks uint8 [N, H, W], status int32 [N]) on `device`, nothing read back."""
-    from .. import ops
-    h, w = (int(v) for v in rles[0]["size"])
+def _rle_concat(rles: Sequence[Dict[str, Any]], what: str, size=None) -> Tuple[np.ndarray, np.ndarray, int, int]:
+    """RLE dicts of ONE frame size -> (all counts int32, concatenated; offsets int64 [N + 1]; h; w), the layout the kernels read."""
+    h, w = (int(v) for v in (rles[0]["size"] if size is None else size))
     cs = []
     for r in rles:
         if [int(v) for v in r["size"]] != [h, w]:
-            raise _lib.UllsamError(f"rle_to_mask_device: records of different sizes ({r['size']} vs {[h, w]})")
+            raise _lib.UllsamError(f"{what}: records of different sizes ({r['size']} vs {[h, w]})")
         cs.append(np.clip(np.asarray(r["counts"], dtype=np.int64).reshape(-1), -1, 2 ** 31 - 1))     # (out-of-range counts stay wrong)
     offs = np.concatenate([[0], np.cumsum([len(c) for c in cs])]).astype(np.int64)
     flat = np.concatenate(cs).astype(np.int32) if offs[-1] else np.zeros((1,), np.int32)
+    return flat, offs, h, w
+
+
+def _rle_expand(rles: Sequence[Dict[str, Any]], device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """RLE dicts of ONE frame size -> (masks uint8 [N, H, W], status int32 [N]) on `device`, nothing read back."""
+    from .. import ops
+    flat, offs, h, w = _rle_concat(rles, "rle_to_mask_device")
     return ops.rle_to_mask(torch.from_numpy(flat).to(device), torch.from_numpy(offs).to(device), h, w)
 
 
@@ -492,3 +498,144 @@ def remove_small_regions_batched(masks: torch.Tensor, area_thresh: float, mode: 
                 labels[s:s + step].copy_(lab)
     res = out.view(torch.bool) if masks.dtype == torch.bool else out
     return (res, changed.bool(), labels) if return_labels else (res, changed.bool())
+
+
+# ---- instance label maps (csrc/labels.hip) --------------------------------------------------------------------------------------
+def paint_ranks(rles: Sequence[Dict[str, Any]], order: str = "record", keys=None) -> np.ndarray:
+    """rank int32 [N]: the place of every record in the paint order (later = on top).  "record": list order, the app's (app.py:707);
+    "area": descending mask area (keys, or the areas the counts give), so small objects end up on top of large ones; "score": ascending
+    keys (predicted_iou).  Ties go by ascending record index.  Host work: N is small."""
+    n = len(rles)
+    idx = np.arange(n)
+    if order == "record":
+        perm = idx
+    elif order == "area":
+        k = np.asarray([area_from_rle(r) for r in rles] if keys is None else keys).reshape(-1)
+        perm = np.lexsort((idx, -k.astype(np.float64) if k.dtype.kind == "f" else -k.astype(np.int64)))
+    elif order == "score":
+        if keys is None:
+            raise ValueError('order="score" needs keys (one predicted_iou per record)')
+        perm = np.lexsort((idx, np.asarray(keys, dtype=np.float64).reshape(-1)))
+    else:
+        raise ValueError(f'order must be "record", "area" or "score", got {order!r}')
+    if len(perm) != n:
+        raise ValueError(f"{len(perm)} keys for {n} records")
+    rank = np.empty((n,), np.int32)
+    rank[perm] = idx
+    return rank
+
+
+def _paint_label_map_host(rles, rank: np.ndarray, h: int, w: int, min_visible_area: int):
+    """The definition: overwrite in paint order (app.py:707 final_mask[mask] = instance_id), visible areas / boxes of the result, drop, renumber."""
+    n = len(rles)
+    raw = np.zeros((h, w), np.int32)
+    for r, i in enumerate(np.argsort(rank, kind="stable")):
+        counts = np.asarray(rles[i]["counts"], dtype=np.int64).reshape(-1)
+        if [int(v) for v in rles[i]["size"]] != [h, w]:
+            raise _lib.UllsamError(f"paint_label_map: records of different sizes ({rles[i]['size']} vs {[h, w]})")
+        if (counts < 0).any() or int(counts.sum()) != h * w:
+            raise _lib.UllsamError(f"paint_label_map: the counts of record {int(i)} are negative or do not sum to H * W")
+        raw[rle_to_mask(rles[i])] = r + 1
+    area_raw = np.bincount(raw.reshape(-1), minlength=n + 1)
+    keep = (area_raw != 0) & (area_raw >= min_visible_area)
+    keep[0] = False
+    lmap = (np.cumsum(keep) * keep).astype(np.int32)
+    labels = lmap[raw]
+    k = int(keep.sum())
+    boxes = np.zeros((k, 4), np.int32)
+    ys, xs = np.nonzero(labels)
+    lab = labels[ys, xs] - 1
+    for col, vals, fn in ((0, xs, np.minimum), (1, ys, np.minimum), (2, xs, np.maximum), (3, ys, np.maximum)):
+        acc = np.full((k,), np.iinfo(np.int32).max if fn is np.minimum else -1, np.int64)
+        fn.at(acc, lab, vals)
+        boxes[:, col] = acc
+    return labels, lmap[rank.astype(np.int64) + 1].astype(np.int32), area_raw[keep].astype(np.int32), boxes
+
+
+def paint_label_map(rles: Sequence[Dict[str, Any]], order: str = "record", keys=None, min_visible_area: int = 0, device=None, size=None):
+    """The instance label image of N records of one frame (uncompressed column-major RLEs, the format of `rle_to_mask`): what the app's
+    save_instance builds by `final_mask[mask] = instance_id` record after record (app.py:688-707), in the paint order `order` (`paint_ranks`).
+    raw[p] = 1 + the largest rank among the records covering p.  A record is DROPPED when its visible area (the pixels that still carry its raw
+    label) is 0 or below `min_visible_area`: its pixels become 0 -- what it had covered is not re-exposed -- and the others are renumbered 1..K in
+    paint order.  -> (labels int32 [H, W], label_of_record int32 [N] (0 = dropped), areas int32 [K], boxes int32 [K, 4] inclusive XYXY; entry
+    l - 1 belongs to label l).  On a GPU `device` the records are painted straight from their counts (no per-record mask exists) and only the
+    status flags and K are read back, in one copy; on the CPU (device None / "cpu") the numpy definition above runs.  `size` = (H, W) is needed
+    when there are no records.  Counts that are negative or do not sum to H * W raise UllsamError."""
+    n = len(rles)
+    if n == 0 and size is None:
+        raise ValueError("paint_label_map: no records and no size")
+    if n > 65535:
+        raise _lib.UllsamError(f"paint_label_map: {n} records (at most 65535)")
+    h, w = (int(v) for v in (rles[0]["size"] if size is None else size))
+    rank = paint_ranks(rles, order, keys)
+    mva = int(min(max(int(min_visible_area), 0), 2 ** 31 - 1))
+    dev = torch.device("cpu" if device is None else device)
+    if dev.type != "cuda":
+        return tuple(torch.from_numpy(np.ascontiguousarray(x)) for x in _paint_label_map_host(rles, rank, h, w, mva))
+    from .. import ops
+    flat, offs, h, w = _rle_concat(rles, "paint_label_map", size=(h, w))
+    rank_d = torch.from_numpy(rank).to(dev)
+    flags = torch.empty((n + 1,), dtype=torch.int32, device=dev)                  # status [N] | K: the one read-back
+    raw, _ = ops.rle_paint_labels(torch.from_numpy(flat).to(dev), torch.from_numpy(offs).to(dev), rank_d, h, w, status=flags[:n])
+    areas_raw, boxes_raw = ops.label_stats(raw, n)
+    lmap, of_record, areas, boxes, _ = ops.label_compact(areas_raw, boxes_raw, rank_d, mva, k_out=flags[n:])
+    labels = ops.label_remap(raw, lmap)
+    fl = flags.cpu().numpy()
+    bad = np.nonzero(fl[:n])[0]
+    if len(bad):
+        raise _lib.UllsamError(f"paint_label_map: the counts of record {int(bad[0])} ({len(bad)} in all) are negative or do not sum to H * W")
+    k = int(fl[n])
+    return labels, of_record, areas[:k], boxes[:k]
+
+
+def _host_array(x):
+    return x.numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def label_overlap(a, b, na=None, nb=None):
+    """The contingency table of two label images of one size, ids in 0..na / 0..nb: T[i, j] = #{p : a[p] = i and b[p] = j}, int64 [na + 1, nb + 1].
+    na / nb default to the images' largest ids (on the GPU that is a read-back; pass them when known).  An id outside its range raises
+    UllsamError.  GPU tensors -> a GPU tensor (one kernel, one 64-bit atomic per run of equal pairs); CPU tensors / arrays -> the numpy form."""
+    gpu = [x.device for x in (a, b) if isinstance(x, torch.Tensor) and x.is_cuda]
+    if gpu:                                                                        # either image on the GPU: the other one follows it there
+        from .. import ops
+        a32, b32 = (torch.as_tensor(x, device=gpu[0]).to(torch.int32).contiguous() for x in (a, b))
+        na = int(a32.max()) if na is None else int(na)
+        nb = int(b32.max()) if nb is None else int(nb)
+        table, status = ops.label_overlap(a32, b32, na, nb)
+        if int(status.item()):
+            raise _lib.UllsamError(f"label_overlap: an id lies outside 0..{na} (a) / 0..{nb} (b)")
+        return table
+    an, bn = _host_array(a).astype(np.int64), _host_array(b).astype(np.int64)
+    if an.shape != bn.shape or an.ndim != 2:
+        raise ValueError(f"label_overlap: two label images of one size, got {an.shape} and {bn.shape}")
+    na = int(an.max(initial=0)) if na is None else int(na)
+    nb = int(bn.max(initial=0)) if nb is None else int(nb)
+    if na < 0 or nb < 0 or (na + 1) * (nb + 1) > 2 ** 26:
+        raise _lib.UllsamError(f"label_overlap: the table [{na + 1}, {nb + 1}] must have between 1 and 2^26 cells")
+    if an.size and (an.min() < 0 or an.max() > na or bn.min() < 0 or bn.max() > nb):
+        raise _lib.UllsamError(f"label_overlap: an id lies outside 0..{na} (a) / 0..{nb} (b)")
+    table = np.bincount((an * (nb + 1) + bn).reshape(-1), minlength=(na + 1) * (nb + 1)).astype(np.int64).reshape(na + 1, nb + 1)
+    return torch.from_numpy(table) if isinstance(a, torch.Tensor) else table
+
+
+def nearest_source_index(n_out: int, n_in: int) -> np.ndarray:
+    """src = min(((2 dst + 1) * n_in) // (2 * n_out), n_in - 1): floor((dst + 0.5) * n_in / n_out) in integers, the rule of PIL's
+    Image.NEAREST resize and of torch's "nearest-exact"."""
+    d = np.arange(n_out, dtype=np.int64)
+    return np.minimum(((2 * d + 1) * n_in) // (2 * n_out), n_in - 1)
+
+
+def resize_labels_nearest(labels, out_hw, window=None):
+    """A label image [H, W] resized to out_hw by the rule above (app.py:807-826 export_mask: Image.NEAREST), optionally only the window
+    (top, left, h, w) of the result (the app's reverse_padding).  GPU tensors -> int32 on the GPU; CPU tensors / arrays keep their dtype."""
+    oh, ow = (int(v) for v in out_hw)
+    top, left, h, w = (0, 0, oh, ow) if window is None else (int(v) for v in window)
+    if isinstance(labels, torch.Tensor) and labels.is_cuda:
+        from .. import ops
+        return ops.resize_nearest_i32(labels.to(torch.int32).contiguous(), (oh, ow), (top, left, h, w))
+    x = _host_array(labels)
+    if x.ndim != 2 or min(x.shape) < 1 or oh < 1 or ow < 1 or min(top, left, h, w) < 0 or top + h > oh or left + w > ow:
+        raise _lib.UllsamError(f"resize_labels_nearest: window {(top, left, h, w)} must lie inside the resized image {(oh, ow)} of a non-empty 2-D image")
+    out = x[nearest_source_index(oh, x.shape[0])[top:top + h, None], nearest_source_index(ow, x.shape[1])[None, left:left + w]]
+    return torch.from_numpy(np.ascontiguousarray(out)) if isinstance(labels, torch.Tensor) else out
