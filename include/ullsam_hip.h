@@ -391,6 +391,33 @@ int ullsam_label_overlap(const int* a, const int* b, int H, int W, int na, int n
 int ullsam_resize_nearest_i32(const int* in, long in_ld, int IH, int IW, int OH, int OW, int top, int left, int h, int w, int* out,
                               long out_ld, void* stream);                                     /* app.py:807-826, 145 reverse_padding */
 
+/* Point prompts, boxes and per-instance masks from one instance label image (csrc/prompts.hip; the reference's dataset loop
+   train_joint_v2.py:313-468 as integer kernels, bit-exact with utils.prompts' host route; definitions in DESIGN.md "7b, continued (prompts)").
+   labels i32 [H, W], 0 = background, ids 1..65535; H * W < 2^31; radius, hi <= 64; num_pos, num_neg <= 16.
+   label_d1: d1 u8 [H, W] = min(radius + 1, city-block distance to the nearest pixel whose label differs, the outside of the frame counting as
+     different); rowdist u8 [H, W] is scratch; status i32 [1] is set to 1 when a label lies outside 0..65535.
+   prompt_choose: areas i32 [65536] (label_stats, N = 65535) -> sel i32 [max_instances] = the present ids in increasing order or, when there
+     are more, max_instances of them by the draw rule; info[0] = how many.  present i32 [65535], sorted i32 [max_instances]: scratch.
+   prompt_sets: for slot s < min(info[0], slots) with id sel[s], the interior {label = id, d1 > radius} and the ring {label != id,
+     lo^2 <= D2 <= hi^2} as bit rows: bits u64 [2, slots, H, ceil(W / 64)] (only the words of the instance's window -- its box grown by hi --
+     are written), rowcnt i32 [2, slots, H], sums u64 [slots, 2] = (sum x, sum y) over the instance.  boxes_t = label_stats' boxes of the
+     label image read as a transposed map.  dbg_inner / dbg_ring u8 [slots, H, W] (both or neither): the two sets as images.
+   prompt_points: coords f32 [slots, num_pos + num_neg, 2] (x, y), boxes f32 [slots, 4] XYXY inclusive, counts i32 [slots, 2] = (|inner|, |ring|),
+     info[2 + 4 s ..] = (id, area, |inner|, |ring|); area 0 marks an absent id.  The negatives of a slot with |ring| < num_neg are left to the
+     caller (the fallbacks).
+   instance_masks: masks f32 [N, per] = (labels == ids[n]). */
+int ullsam_label_d1(const int* labels, int H, int W, int radius, unsigned char* rowdist, unsigned char* d1, int* status,
+                    void* stream);                                                            /* train_joint_v2.py:342 */
+int ullsam_prompt_choose(const int* areas, int max_instances, unsigned long long seed, int* present, int* sorted, int* sel, int* info,
+                         void* stream);                                                       /* train_joint_v2.py:319-327 */
+int ullsam_prompt_sets(const int* labels, const unsigned char* d1, int H, int W, const int* areas, const int* boxes_t, const int* sel,
+                       const int* info, int slots, int radius, int lo, int hi, unsigned long long* bits, int* rowcnt,
+                       unsigned long long* sums, unsigned char* dbg_inner, unsigned char* dbg_ring, void* stream);   /* :342, 423-437 */
+int ullsam_prompt_points(int H, int W, const int* areas, const int* boxes_t, const int* sel, int* info, int slots, int hi, int num_pos,
+                         int num_neg, unsigned long long seed, const unsigned long long* bits, const int* rowcnt,
+                         const unsigned long long* sums, float* coords, float* boxes, int* counts, void* stream);    /* :353-381, 439-442 */
+int ullsam_instance_masks(const int* labels, const int* ids, long N, long per, float* masks, void* stream);          /* :332 */
+
 /* fp8 (OCP e4m3) ViT path -- BASELINE.json configs[4]; the reference's bf16 encoder linears image_encoder.py:227,171-181 with
    8-bit operands: rows quantised with a per-row scale (optionally behind the block's LayerNorm :166,180), GEMM on the
    block-scaled fp8 MFMA, scales applied in the epilogue */

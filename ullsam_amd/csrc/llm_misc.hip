@@ -1,5 +1,6 @@
 // HBM-bound kernels around the InternLM2 decoder stack.
 #include "common.h"
+#include "philox.h"
 
 // ---- image-token scan (modeling_internvl_sam.py:135-139,194-199) -------------------------------------------------
 // ids int64 [B,S] -> rank int32 [B,S] (k-th image token of the sample, or -1) and range int32 [B,2] = [min_idx, max_idx+1)
@@ -210,18 +211,9 @@ __device__ __forceinline__ unsigned int sample_key(float x) {   // larger value 
 }
 __device__ __forceinline__ float sample_value(unsigned int k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
-// Philox4x32-10 (Salmon et al., SC'11; Random123), word 0 of the block with counter (step lo, step hi, 0, 0) and key (seed lo, seed hi)
+// Philox4x32-10 (philox.h), word 0 of the block with counter (step lo, step hi, 0, 0) and key (seed lo, seed hi)
 __device__ __forceinline__ unsigned int philox4x32_10_word0(unsigned long long seed, unsigned long long step) {
-    unsigned int c0 = (unsigned int)step, c1 = (unsigned int)(step >> 32), c2 = 0u, c3 = 0u;
-    unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned int h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const unsigned int h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return c0;
+    return philox4x32_10_word0((unsigned int)seed, (unsigned int)(seed >> 32), (unsigned int)step, (unsigned int)(step >> 32), 0u, 0u);
 }
 
 template <typename T> __device__ __forceinline__ T wave_scan_incl(T v, int lane) {

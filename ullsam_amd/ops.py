@@ -885,3 +885,108 @@ def resize_nearest_i32(x: torch.Tensor, out_hw, window=None) -> torch.Tensor:
     out = torch.empty((h, w), dtype=torch.int32, device=x.device)
     _lib.call("ullsam_resize_nearest_i32", x.data_ptr(), iw, ih, iw, oh, ow, top, left, h, w, out.data_ptr(), w, _stream())
     return out
+
+
+# ---- prompts from an instance label image (csrc/prompts.hip) ----------------------------------------------------------------------
+PROMPT_MAX_ID = 65535
+PROMPT_MAX_RADIUS = 64
+PROMPT_MAX_POINTS = 16
+
+
+def label_d1(labels: torch.Tensor, radius: int, status: Optional[torch.Tensor] = None):
+    """labels int32 [h, w] -> (d1 uint8 [h, w] = min(radius + 1, city-block distance to the nearest pixel with another label, the outside of the
+    frame counting as another label); status int32 [1], set to 1 when a label lies outside 0..65535 -- the caller zeroes and reads it)."""
+    _chk(labels, "labels", torch.int32)
+    assert labels.dim() == 2
+    h, w = labels.shape
+    if not 0 <= int(radius) <= PROMPT_MAX_RADIUS:
+        raise _lib.UllsamError(f"label_d1: radius {radius} is outside 0..{PROMPT_MAX_RADIUS}")
+    scratch = torch.empty((h, w), dtype=torch.uint8, device=labels.device)
+    d1 = torch.empty((h, w), dtype=torch.uint8, device=labels.device)
+    if status is None:
+        status = torch.zeros((1,), dtype=torch.int32, device=labels.device)
+    else:
+        _chk(status, "status", torch.int32)
+    _lib.call("ullsam_label_d1", labels.data_ptr(), h, w, int(radius), scratch.data_ptr(), d1.data_ptr(), status.data_ptr(), _stream())
+    return d1, status
+
+
+def prompt_choose(areas: torch.Tensor, max_instances: int, seed: int, info: Optional[torch.Tensor] = None):
+    """areas int32 [65536] (label_stats with n = 65535) -> (sel int32 [max_instances]: the present ids in increasing order, or max_instances of them
+    by the draw rule when more are present; info int32 [2 + 4 * max_instances] with info[0] = how many were chosen)."""
+    _chk(areas, "areas", torch.int32)
+    assert areas.numel() == PROMPT_MAX_ID + 1
+    m = int(max_instances)
+    if not 1 <= m <= PROMPT_MAX_ID:
+        raise _lib.UllsamError(f"prompt_choose: max_instances {m} is outside 1..{PROMPT_MAX_ID}")
+    dev = areas.device
+    present = torch.empty((PROMPT_MAX_ID,), dtype=torch.int32, device=dev)
+    sorted_ = torch.empty((m,), dtype=torch.int32, device=dev)
+    sel = torch.zeros((m,), dtype=torch.int32, device=dev)
+    if info is None:
+        info = torch.zeros((2 + 4 * m,), dtype=torch.int32, device=dev)
+    else:
+        _chk(info, "info", torch.int32)
+        assert info.numel() >= 2 + 4 * m
+    _lib.call("ullsam_prompt_choose", areas.data_ptr(), m, int(seed) % (1 << 64), present.data_ptr(), sorted_.data_ptr(), sel.data_ptr(),
+              info.data_ptr(), _stream())
+    return sel, info
+
+
+def prompt_sets(labels: torch.Tensor, d1: torch.Tensor, areas: torch.Tensor, boxes_t: torch.Tensor, sel: torch.Tensor, info: torch.Tensor,
+                radius: int, ring, debug: bool = False):
+    """The interior and ring candidate sets of the slots s < info[0] (ids sel[s]) as bit rows -> (bits int64 [2, slots, h, ceil(w / 64)], rowcnt int32
+    [2, slots, h], sums int64 [slots, 2] = (sum x, sum y) over the instance, dbg: None or (inner, ring) uint8 [slots, h, w]).  areas / boxes_t:
+    label_stats(labels, 65535) -- the label image read as a transposed map, so a box there is (y0, x0, y1, x1).  The outputs are sized by the slots,
+    used or not (h * ceil(w / 64) * 16 + h * 8 bytes each): utils.prompts bounds them before it calls."""
+    for t, name, dt in ((labels, "labels", torch.int32), (d1, "d1", torch.uint8), (areas, "areas", torch.int32), (boxes_t, "boxes_t", torch.int32),
+                        (sel, "sel", torch.int32), (info, "info", torch.int32)):
+        _chk(t, name, dt)
+    h, w = labels.shape
+    slots = sel.numel()
+    lo, hi = (int(v) for v in ring)
+    assert d1.shape == labels.shape and areas.numel() == PROMPT_MAX_ID + 1 and boxes_t.numel() == 4 * (PROMPT_MAX_ID + 1) and info.numel() >= 2 + 4 * slots
+    if not (0 <= int(radius) <= PROMPT_MAX_RADIUS and 0 <= lo <= hi <= PROMPT_MAX_RADIUS and 1 <= slots <= PROMPT_MAX_ID):
+        raise _lib.UllsamError(f"prompt_sets: need 0 <= radius <= {PROMPT_MAX_RADIUS}, 0 <= ring[0] <= ring[1] <= {PROMPT_MAX_RADIUS} and 1..{PROMPT_MAX_ID} slots")
+    dev = labels.device
+    bits = torch.empty((2, slots, h, (w + 63) // 64), dtype=torch.int64, device=dev)
+    rowcnt = torch.empty((2, slots, h), dtype=torch.int32, device=dev)
+    sums = torch.empty((slots, 2), dtype=torch.int64, device=dev)
+    dbg = (torch.empty((slots, h, w), dtype=torch.uint8, device=dev), torch.empty((slots, h, w), dtype=torch.uint8, device=dev)) if debug else None
+    _lib.call("ullsam_prompt_sets", labels.data_ptr(), d1.data_ptr(), h, w, areas.data_ptr(), boxes_t.data_ptr(), sel.data_ptr(), info.data_ptr(), slots,
+              int(radius), lo, hi, bits.data_ptr(), rowcnt.data_ptr(), sums.data_ptr(), _p(dbg[0]) if dbg else None, _p(dbg[1]) if dbg else None, _stream())
+    return bits, rowcnt, sums, dbg
+
+
+def prompt_points(hw, areas: torch.Tensor, boxes_t: torch.Tensor, sel: torch.Tensor, info: torch.Tensor, bits: torch.Tensor, rowcnt: torch.Tensor,
+                  sums: torch.Tensor, hi: int, num_pos: int, num_neg: int, seed: int):
+    """The points of every slot from its candidate sets (prompt_sets) by the draw rule -> (coords float32 [slots, num_pos + num_neg, 2] as (x, y),
+    boxes float32 [slots, 4] XYXY inclusive, counts int32 [slots, 2] = (|inner|, |ring|)); info[2 + 4 s ..] = (id, area, |inner|, |ring|).  The
+    negatives of a slot with |ring| < num_neg stay zero: the caller applies the fallbacks."""
+    for t, name, dt in ((areas, "areas", torch.int32), (boxes_t, "boxes_t", torch.int32), (sel, "sel", torch.int32), (info, "info", torch.int32),
+                        (bits, "bits", torch.int64), (rowcnt, "rowcnt", torch.int32), (sums, "sums", torch.int64)):
+        _chk(t, name, dt)
+    h, w = (int(v) for v in hw)
+    slots = sel.numel()
+    assert bits.shape == (2, slots, h, (w + 63) // 64) and rowcnt.shape == (2, slots, h) and sums.shape == (slots, 2) and info.numel() >= 2 + 4 * slots
+    if not (0 <= int(num_pos) <= PROMPT_MAX_POINTS and 0 <= int(num_neg) <= PROMPT_MAX_POINTS and 0 <= int(hi) <= PROMPT_MAX_RADIUS):
+        raise _lib.UllsamError(f"prompt_points: need num_pos, num_neg <= {PROMPT_MAX_POINTS} and ring[1] <= {PROMPT_MAX_RADIUS}")
+    dev = sel.device
+    coords = torch.zeros((slots, int(num_pos) + int(num_neg), 2), dtype=torch.float32, device=dev)
+    boxes = torch.zeros((slots, 4), dtype=torch.float32, device=dev)
+    counts = torch.zeros((slots, 2), dtype=torch.int32, device=dev)
+    _lib.call("ullsam_prompt_points", h, w, areas.data_ptr(), boxes_t.data_ptr(), sel.data_ptr(), info.data_ptr(), slots, int(hi), int(num_pos),
+              int(num_neg), int(seed) % (1 << 64), bits.data_ptr(), rowcnt.data_ptr(), sums.data_ptr(), coords.data_ptr(), boxes.data_ptr(),
+              counts.data_ptr(), _stream())
+    return coords, boxes, counts
+
+
+def instance_masks(labels: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """labels int32 [h, w], ids int32 [n] -> float32 [n, h, w] = (labels == ids[i])."""
+    _chk(labels, "labels", torch.int32); _chk(ids, "ids", torch.int32)
+    h, w = labels.shape
+    n = ids.numel()
+    assert n <= PROMPT_MAX_ID
+    out = torch.empty((n, h, w), dtype=torch.float32, device=labels.device)
+    _lib.call("ullsam_instance_masks", labels.data_ptr(), ids.data_ptr(), n, h * w, out.data_ptr(), _stream())
+    return out

@@ -1461,7 +1461,9 @@ def train_step_loss(model, pixel_values: torch.Tensor, input_ids: torch.Tensor, 
     model(...) with output_hidden_states (the vision features enter the LLM path under no_grad, modeling_internvl_sam.py:243-244), the second
     vision_model(pixel_values) call with gradients for the decoder, prompt encoder, mask decoder, upsample, BCE + Dice.  One vision-model
     forward serves both uses (same values; the LLM path takes it detached).  Returns (total, bce, dice); total.backward() fills the
-    gradients of vision_model, mlp1, mlp2, prompt_encoder and mask_decoder parameters that require them."""
+    gradients of vision_model, mlp1, mlp2, prompt_encoder and mask_decoder parameters that require them.
+    `points` and `gt_masks` are what the reference's dataset derives from the sample's instance label image (train_joint_v2.py:313-468);
+    utils.prompts.prompts_from_labels(labels, device=...) derives them on the GPU: pass (ps.coords, ps.point_labels) and ps.masks unchanged."""
     rows = vision_feature_rows(model.vision_model, pixel_values)
     hidden = llm_image_hidden(model, rows.detach(), input_ids, attention_mask)
     return segmentation_loss(model, hidden, None, points, gt_masks, image_rows=rows)

@@ -15,18 +15,26 @@ from typing import Tuple
 import numpy as np
 
 
-def microscopy_tile(seed: int, size: int = 1024, n_cells: int = 14, r_range: Tuple[float, float] = (70.0, 150.0),
-                    bg: float = 0.1, fg: float = 0.8, noise: float = 0.02) -> Tuple[np.ndarray, np.ndarray]:
-    """-> (image float32 [3, size, size] in [0, 1], cell centres float32 [n_cells, 2] as (x, y) pixel coordinates).
-    Deterministic in `seed` (numpy default_rng: the same tile on the GPU box and in the build container)."""
+def _cells(seed: int, size: int, n_cells: int, r_range: Tuple[float, float]):
+    """The cells of a tile: (the generator after the draws, cx, cy, r, an iterator over each cell's disc as a bool [size, size]) -- the one place the
+    draws and the disc test live, shared by microscopy_tile and label_tile."""
     rng = np.random.default_rng([int(seed), 0x5EED])
     cx = rng.uniform(0, size, n_cells)
     cy = rng.uniform(0, size, n_cells)
     r = rng.uniform(r_range[0], r_range[1], n_cells)
     yy, xx = np.mgrid[0:size, 0:size].astype(np.float32)
+    discs = ((xx - np.float32(cx[i])) ** 2 + (yy - np.float32(cy[i])) ** 2 < np.float32(r[i]) ** 2 for i in range(n_cells))
+    return rng, cx, cy, r, discs
+
+
+def microscopy_tile(seed: int, size: int = 1024, n_cells: int = 14, r_range: Tuple[float, float] = (70.0, 150.0),
+                    bg: float = 0.1, fg: float = 0.8, noise: float = 0.02) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (image float32 [3, size, size] in [0, 1], cell centres float32 [n_cells, 2] as (x, y) pixel coordinates).
+    Deterministic in `seed` (numpy default_rng: the same tile on the GPU box and in the build container)."""
+    rng, cx, cy, _, discs = _cells(seed, size, n_cells, r_range)
     inside = np.zeros((size, size), bool)
-    for i in range(n_cells):
-        inside |= (xx - np.float32(cx[i])) ** 2 + (yy - np.float32(cy[i])) ** 2 < np.float32(r[i]) ** 2
+    for disc in discs:
+        inside |= disc
     img = np.where(inside, np.float32(fg), np.float32(bg)) + np.float32(noise) * rng.standard_normal((size, size), dtype=np.float32)
     img = np.clip(img, 0.0, 1.0).astype(np.float32)
     centres = np.stack([cx, cy], 1).astype(np.float32)
@@ -42,6 +50,15 @@ def microscopy_batch(seeds, size: int = 1024, **kw) -> Tuple[np.ndarray, np.ndar
         imgs.append(im)
         pts.append(np.clip(c[k], 0, size - 1))
     return np.stack(imgs), np.stack(pts)[:, None, :].astype(np.float32)
+
+
+def label_tile(seed: int, size: int = 1024, n_cells: int = 14, r_range: Tuple[float, float] = (70.0, 150.0)) -> np.ndarray:
+    """-> int32 [size, size] instance label image of microscopy_tile's discs (the same draws): cell i carries id i + 1, later cells on top, 0 is the
+    background.  A cell that later cells hide completely leaves its id absent."""
+    labels = np.zeros((size, size), np.int32)
+    for i, disc in enumerate(_cells(seed, size, n_cells, r_range)[4]):
+        labels[disc] = i + 1
+    return labels
 
 
 def param_init_rule(name: str, shape) -> Tuple[float, float]:
