@@ -418,6 +418,31 @@ int ullsam_prompt_points(int H, int W, const int* areas, const int* boxes_t, con
                          const unsigned long long* sums, float* coords, float* boxes, int* counts, void* stream);    /* :353-381, 439-442 */
 int ullsam_instance_masks(const int* labels, const int* ids, long N, long per, float* masks, void* stream);          /* :332 */
 
+/* Image preprocessing (csrc/imageprep.hip): Pillow's antialiased 8-bit resize as two integer passes, bit-exact with PIL.Image.resize
+   (Resample.c, 8 bits per channel; definitions in DESIGN.md "7b, continued (image preprocessing)"), and the app's min-max normalisation to
+   uint8.  The bounds (first tap, tap count) and 22-bit fixed-point coefficient tables are built on the host in float64 (ops.aa_tables).
+   resize_u8_aa_h: src u8 addressed as y * s_row + x * s_col + c * s_chan (interleaved [IH, IW, C] or planar [C, IH, IW]), C in {1, 3, 4}, placed
+     at (top, left) of a virtual [VH, VW] image that is zero elsewhere (the app's centred pad_to_square as a parameter); virtual rows
+     row0 .. row0 + rows - 1 -- those the vertical pass reads -- are resampled to OW columns into tmp u8 [rows, OW, C].  bounds i32 [OW, 2],
+     coef i32 [ksize, OW] (tap-major).
+   resize_u8_aa_v: tmp -> OH rows; bounds i32 [OH, 2] (first row as a virtual row, row0 <= first, first + count <= row0 + rows), coef i32
+     [OH, ksize].  Writes out_u8 [OH, OW, C] and / or out_f32: plane c = 0..2 at c * f_plane + y * f_row + x holds lut[c * 256 + v], lut f32
+     [3, 256] (ToTensor + Normalize as 256 values per channel computed by the host with the reference's torch ops); only the OH x OW corner of
+     each plane is written; C == 1 feeds all three planes (convert("RGB")), the fourth channel of C == 4 has no plane.
+   minmax_*: mm u32 [2] = (min, max) as order-preserving keys (the value for u16; sign-flipped bits for f32), by integer atomics.
+   normalize_to_u8_*: ((x - min) / (max - min + 1e-8) * 255).astype(uint8) as numpy evaluates it: u16 -- difference in uint16, quotient and
+     product in float64; f32 -- all in float32; truncation.  NaN inputs are out of scope. */
+int ullsam_resize_u8_aa_h(const unsigned char* src, long s_row, long s_col, long s_chan, int IH, int IW, int C, int top, int left, int VH,
+                          int VW, int row0, int rows, const int* bounds, const int* coef, int ksize, int OW, unsigned char* tmp,
+                          void* stream);                      /* utils/transforms.py:26-31, app.py:111-143, 232-248, train_joint_v2.py:271-275 */
+int ullsam_resize_u8_aa_v(const unsigned char* tmp, int row0, int rows, int OW, int C, const int* bounds, const int* coef, int ksize, int OH,
+                          unsigned char* out_u8, const float* lut, float* out_f32, long f_plane, long f_row,
+                          void* stream);                      /* utils/transforms.py:26-31, app.py:242-249, train_joint_v2.py:299-300 */
+int ullsam_minmax_u16(const unsigned short* x, long n, unsigned* mm, void* stream);                                  /* app.py:190-191 */
+int ullsam_minmax_f32(const float* x, long n, unsigned* mm, void* stream);                                           /* app.py:226-228 */
+int ullsam_normalize_to_u8_u16(const unsigned short* x, long n, const unsigned* mm, unsigned char* out, void* stream);   /* app.py:190-191 */
+int ullsam_normalize_to_u8_f32(const float* x, long n, const unsigned* mm, unsigned char* out, void* stream);            /* app.py:226-228 */
+
 /* fp8 (OCP e4m3) ViT path -- BASELINE.json configs[4]; the reference's bf16 encoder linears image_encoder.py:227,171-181 with
    8-bit operands: rows quantised with a per-row scale (optionally behind the block's LayerNorm :166,180), GEMM on the
    block-scaled fp8 MFMA, scales applied in the epilogue */

@@ -103,6 +103,12 @@ SIGNATURES = {
     "ullsam_prompt_sets": [vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
     "ullsam_prompt_points": [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, C.c_ulonglong, vp, vp, vp, vp, vp, vp, vp],
     "ullsam_instance_masks": [vp, vp, i64, i64, vp, vp],
+    "ullsam_resize_u8_aa_h": [vp, i64, i64, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp],
+    "ullsam_resize_u8_aa_v": [vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, i64, i64, vp],
+    "ullsam_minmax_u16": [vp, i64, vp, vp],
+    "ullsam_minmax_f32": [vp, i64, vp, vp],
+    "ullsam_normalize_to_u8_u16": [vp, i64, vp, vp, vp],
+    "ullsam_normalize_to_u8_f32": [vp, i64, vp, vp, vp],
     "ullsam_rows_fp8": [vp, i32, i64, vp, i64, vp, vp, vp, i64, i32, f32, vp],
     "ullsam_gemm_fp8": [vp, i64, vp, vp, i64, vp, vp, i64, i32, vp, vp, i64, i32, i32, i32, i32, vp],
     "ullsam_rows_fp8_pow2": [vp, i32, i64, vp, i64, vp, i64, i32, vp],

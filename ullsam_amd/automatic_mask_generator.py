@@ -8,8 +8,11 @@ stability >= stability_score_thresh; drop boxes touching an interior crop edge; 
 small crops).  Helper parity is pinned (tests/golden/amg.npz); driver parity is checked against a numpy re-statement of the same
 flow over the oracle (tests/test_amg_gpu.py).
 
-Deviations, stated: images are resized with the bilinear kernel (align_corners=False, no antialias) instead of PIL's antialiased
-uint8 resize; `min_mask_region_area` post-processing labels regions on the GPU (csrc/regions.hip: batched 8-connected union-find,
+Deviations, stated: with `image_resize="bilinear"` (default) a crop is resized as float32 with the bilinear kernel (align_corners=False,
+no antialias); with `image_resize="pil"` the image must be uint8 and a crop is resized as ResizeLongestSide.apply_image does it in Meta's
+predictor -- PIL's antialiased uint8 resize, bit-exact (csrc/imageprep.hip, identity table: the float value of each byte) -- before it
+enters the encoder; a crop whose longest side already equals img_size is not resized under either setting, and the records are the same;
+`min_mask_region_area` post-processing labels regions on the GPU (csrc/regions.hip: batched 8-connected union-find,
 utils.amg.remove_small_regions_batched) instead of OpenCV on the host -- only region membership and integer sizes are used, so the
 records are the same bits; `device_small_regions=False` runs the host form of the step (utils.amg.remove_small_regions, scipy as the
 labeller), which is the definition the device path is tested against, and is what a model on the CPU gets;
@@ -37,11 +40,14 @@ class SamAutomaticMaskGenerator:
                  crop_n_layers: int = 0, crop_nms_thresh: float = 0.7, crop_overlap_ratio: float = 512 / 1500,
                  crop_n_points_downscale_factor: int = 1, point_grids: Optional[List[np.ndarray]] = None,
                  min_mask_region_area: int = 0, output_mode: str = "binary_mask", fused_postprocess: bool = True,
-                 device_small_regions: bool = True) -> None:
+                 device_small_regions: bool = True, image_resize: str = "bilinear") -> None:
         assert (points_per_side is None) != (point_grids is None), "Exactly one of points_per_side or point_grid must be provided."
         self.point_grids = (A.build_all_layer_point_grids(points_per_side, crop_n_layers, crop_n_points_downscale_factor)
                             if points_per_side is not None else point_grids)
         assert output_mode in ("binary_mask", "uncompressed_rle", "coco_rle"), f"Unknown output_mode {output_mode}."
+        if image_resize not in ("bilinear", "pil"):
+            raise ValueError(f"image_resize must be 'bilinear' or 'pil', got {image_resize!r}")
+        self.image_resize = image_resize
         self.min_mask_region_area = int(min_mask_region_area)
         self.model = model
         self.points_per_batch = points_per_batch
@@ -58,16 +64,25 @@ class SamAutomaticMaskGenerator:
 
     # -- image side --------------------------------------------------------------------------------------------------
     def _encode(self, crop: torch.Tensor):
-        """crop fp32 [3,h,w] in 0..255 -> (image tokens [1,N,C], input_size (h', w') in the 1024 frame)."""
+        """crop [3,h,w] in 0..255, fp32 or (image_resize="pil") uint8 -> (image tokens [1,N,C], input_size (h', w') in the 1024 frame)."""
         sam = self.model
         S = sam.image_encoder.img_size
         h, w = crop.shape[-2:]
         scale = S / max(h, w)
         nh, nw = int(h * scale + 0.5), int(w * scale + 0.5)  # ResizeLongestSide.get_preprocess_shape (utils/transforms.py:93-102)
-        x = crop if (nh, nw) == (h, w) else ops.resize_bilinear(crop.contiguous(), (nh, nw))[0]
+        if crop.dtype == torch.uint8:                        # the planar crop, as it lies, is the kernels' [h, w, 3] source by strides
+            x = crop.float() if (nh, nw) == (h, w) else ops.resize_u8_aa(crop.permute(1, 2, 0), (nh, nw), lut=self._identity_lut(crop.device), want_u8=False)[1]
+        else:
+            x = crop if (nh, nw) == (h, w) else ops.resize_bilinear(crop.contiguous(), (nh, nw))[0]
         mean = sam.pixel_mean.reshape(-1).float().contiguous()
         std = sam.pixel_std.reshape(-1).float().contiguous()
         return sam.image_encoder.forward_tokens(x[None].contiguous(), mean, std), (nh, nw)
+
+    def _identity_lut(self, device) -> torch.Tensor:
+        lut = getattr(self, "_lut", None)
+        if lut is None or lut.device != device:
+            lut = self._lut = torch.arange(256, dtype=torch.float32, device=device).repeat(3, 1).contiguous()
+        return lut
 
     # -- one batch of point prompts ------------------------------------------------------------------------------------
     def _process_batch(self, points: np.ndarray, img_tok, input_size, crop_box, orig_size, image_cache=None) -> A.MaskData:
@@ -351,7 +366,12 @@ class SamAutomaticMaskGenerator:
         dev = self.model.device
         if isinstance(image, np.ndarray):
             image = torch.from_numpy(np.ascontiguousarray(image)).permute(2, 0, 1)
-        image = image.to(dev).float().contiguous()
+        if self.image_resize == "pil":                       # stays uint8 (1 byte per sample on the device); _encode resizes it exactly
+            if image.dtype != torch.uint8:
+                raise ValueError(f"image_resize='pil' is PIL's 8-bit resize: the image must be uint8 (numpy [H, W, 3] or a uint8 tensor), got {image.dtype}")
+            image = image.to(dev)
+        else:
+            image = image.to(dev).float().contiguous()
         orig_size = tuple(int(v) for v in image.shape[-2:])
         crop_boxes, layer_idxs = A.generate_crop_boxes(orig_size, self.crop_n_layers, self.crop_overlap_ratio)
         data = A.MaskData()
@@ -383,7 +403,7 @@ class SamAutomaticMaskGenerator:
 
     @torch.no_grad()
     def generate(self, image) -> List[Dict[str, Any]]:
-        """image: HxWx3 uint8 / float array (0..255) or a [3,H,W] tensor.  Returns SAM-style records sorted as generated."""
+        """image: HxWx3 uint8 / float array (0..255) or a [3,H,W] tensor (uint8 only with image_resize="pil").  Returns SAM-style records sorted as generated."""
         return self._records(self._generate_data(image)[0], self.output_mode)
 
     @torch.no_grad()

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -989,4 +990,148 @@ def instance_masks(labels: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     assert n <= PROMPT_MAX_ID
     out = torch.empty((n, h, w), dtype=torch.float32, device=labels.device)
     _lib.call("ullsam_instance_masks", labels.data_ptr(), ids.data_ptr(), n, h * w, out.data_ptr(), _stream())
+    return out
+
+
+# ---- image preprocessing (csrc/imageprep.hip) --------------------------------------------------------------------------------------
+AA_FILTERS = ("bilinear", "bicubic")
+AA_BITS = 22
+_AA_HOST = {}
+_AA_DEV = {}
+
+
+def _aa_filter(name: str, x: np.ndarray) -> np.ndarray:
+    x = np.abs(x)
+    if name == "bilinear":
+        return np.where(x < 1.0, 1.0 - x, 0.0)
+    a = -0.5
+    return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1, np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a, 0.0))
+
+
+def aa_tables(in_size: int, out_size: int, filter: str = "bilinear"):
+    """The bounds and coefficients of one axis of Pillow's 8-bit antialiased resize (Resample.c precompute_coeffs + normalize_coeffs_8bpc), in
+    float64 on the host -> (bounds int32 [out, 2] = (first tap, tap count), coef int32 [out, ksize], taps past the count zero).  Cached per
+    (in, out, filter).  in == out is the pass Pillow skips: the identity table (one tap of 2**22), which copies."""
+    if filter not in AA_FILTERS:
+        raise ValueError(f"filter must be one of {AA_FILTERS}, got {filter!r}")
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size <= 0 or out_size <= 0:
+        raise ValueError(f"aa_tables: sizes must be positive, got {in_size} -> {out_size}")
+    key = (in_size, out_size, filter)
+    hit = _AA_HOST.get(key)
+    if hit is not None:
+        return hit
+    if in_size == out_size:
+        bounds = np.stack([np.arange(out_size), np.ones(out_size, np.int64)], 1).astype(np.int32)
+        coef = np.full((out_size, 1), 1 << AA_BITS, np.int32)
+    else:
+        scale = in_size / out_size
+        fs = max(scale, 1.0)
+        support = (1.0 if filter == "bilinear" else 2.0) * fs
+        ksize = int(np.ceil(support)) * 2 + 1
+        ss = 1.0 / fs                                            # (Pillow multiplies by the reciprocal; a division differs in the last bit)
+        center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+        xmin = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+        xmax = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), in_size)
+        n = xmax - xmin
+        t = np.arange(ksize)
+        w = _aa_filter(filter, (t[None, :] + xmin[:, None] - center[:, None] + 0.5) * ss)
+        w[t[None, :] >= n[:, None]] = 0.0
+        ww = np.zeros(out_size, np.float64)
+        for j in range(ksize):                                   # the sum in index order, as the C loop forms it
+            ww = ww + w[:, j]
+        w = np.where((ww != 0.0)[:, None], w / np.where(ww != 0.0, ww, 1.0)[:, None], w)
+        coef = np.where(w < 0, np.trunc(-0.5 + w * (1 << AA_BITS)), np.trunc(0.5 + w * (1 << AA_BITS))).astype(np.int32)
+        bounds = np.stack([xmin, n], 1).astype(np.int32)
+    if len(_AA_HOST) >= 64:
+        _AA_HOST.clear()
+    _AA_HOST[key] = (bounds, coef)
+    return bounds, coef
+
+
+def _aa_tables_dev(in_size: int, out_size: int, filter: str, tap_major: bool, device):
+    """aa_tables on the device, uploaded once per (in, out, filter, layout, device): (bounds, coef, ksize); tap_major -> coef [ksize, out]."""
+    key = (int(in_size), int(out_size), filter, bool(tap_major), str(device))
+    hit = _AA_DEV.get(key)
+    if hit is None:
+        bounds, coef = aa_tables(in_size, out_size, filter)
+        c = np.ascontiguousarray(coef.T if tap_major else coef)
+        if len(_AA_DEV) >= 64:
+            _AA_DEV.clear()
+        hit = _AA_DEV[key] = (torch.from_numpy(bounds).to(device), torch.from_numpy(c).to(device), int(coef.shape[1]))
+    return hit
+
+
+def aa_row_span(in_size: int, out_size: int, filter: str = "bilinear"):
+    """(first, count): the source rows the vertical pass reads -- all the horizontal pass has to compute."""
+    bounds, _ = aa_tables(in_size, out_size, filter)
+    first = int(bounds[:, 0].min())
+    return first, int((bounds[:, 0] + bounds[:, 1]).max()) - first
+
+
+def resize_u8_aa(src: torch.Tensor, out_hw, filter: str = "bilinear", window=None, lut: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None, want_u8: bool = True):
+    """Pillow's antialiased 8-bit resize (Image.resize, BILINEAR / BICUBIC), bit-exact.  src uint8 [H, W, C] or [H, W] with any non-negative
+    strides (a planar [C, H, W] image is passed as chw.permute(1, 2, 0); a crop as a slice), C in {1, 3, 4}.
+    window = (top, left, VH, VW): the image sits at (top, left) of a zero image of VH x VW, and that is what is resized (pad_to_square without the copy).
+    -> (u8, f32): u8 uint8 [OH, OW, C] when want_u8; f32 when `lut` (float32 [3, 256]) is given: float32 [3, S_h >= OH, S_w >= OW] = `out` (a slot of a
+    batch tensor; last stride 1) or a new [3, OH, OW], whose top-left OH x OW of plane c holds lut[c][value] -- the rest of `out` is left untouched."""
+    if not src.is_cuda:
+        raise _lib.UllsamError("src must live on the GPU (ullsam_amd has no CPU path)")
+    if src.device.index != torch.cuda.current_device():
+        raise _lib.UllsamError(f"src lives on {src.device} but the current device is cuda:{torch.cuda.current_device()}")
+    if src.dtype != torch.uint8:
+        raise TypeError(f"src must be torch.uint8, got {src.dtype}")
+    if src.dim() == 2:
+        src = src[:, :, None]
+    if src.dim() != 3 or src.shape[2] not in (1, 3, 4) or src.shape[0] == 0 or src.shape[1] == 0 or min(src.stride()) < 0:
+        raise ValueError(f"src must be a non-empty [H, W, C] image with C in (1, 3, 4) and non-negative strides, got shape {tuple(src.shape)}")
+    IH, IW, C = (int(v) for v in src.shape)
+    OH, OW = (int(v) for v in out_hw)
+    top, left, VH, VW = (0, 0, IH, IW) if window is None else (int(v) for v in window)
+    if not (OH > 0 and OW > 0 and top >= 0 and left >= 0 and top + IH <= VH and left + IW <= VW):
+        raise _lib.UllsamError(f"resize_u8_aa: the image {(IH, IW)} at {(top, left)} does not lie inside the window {(VH, VW)}, or the output size {(OH, OW)} is empty")
+    if lut is None and not want_u8:
+        raise ValueError("resize_u8_aa: nothing to compute (want_u8=False and no lut)")
+    dev = src.device
+    bh, ch, kh = _aa_tables_dev(VW, OW, filter, True, dev)
+    bv, cv, kv = _aa_tables_dev(VH, OH, filter, False, dev)
+    row0, rows = aa_row_span(VH, OH, filter)
+    f32 = None
+    if lut is not None:
+        _chk(lut, "lut", torch.float32)
+        if tuple(lut.shape) != (3, 256):
+            raise ValueError(f"lut must be [3, 256], got {tuple(lut.shape)}")
+        if out is None:
+            f32 = torch.empty((3, OH, OW), dtype=torch.float32, device=dev)
+        else:
+            if not (out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.dim() == 3 and out.shape[0] == 3 and out.shape[1] >= OH
+                    and out.shape[2] >= OW and out.stride(2) == 1 and out.stride(1) >= out.shape[2] and out.stride(0) >= 0):
+                raise ValueError(f"out must be a float32 [3, >= {OH}, >= {OW}] tensor on {dev} with unit last stride, got {tuple(out.shape)} {out.dtype}")
+            f32 = out
+    elif out is not None:
+        raise ValueError("resize_u8_aa: `out` is the float output and needs `lut`")
+    u8 = torch.empty((OH, OW, C), dtype=torch.uint8, device=dev) if want_u8 else None
+    tmp = torch.empty((rows, OW, C), dtype=torch.uint8, device=dev)
+    _lib.call("ullsam_resize_u8_aa_h", src.data_ptr(), src.stride(0), src.stride(1), src.stride(2), IH, IW, C, top, left, VH, VW, row0, rows,
+              bh.data_ptr(), ch.data_ptr(), kh, OW, tmp.data_ptr(), _stream())
+    _lib.call("ullsam_resize_u8_aa_v", tmp.data_ptr(), row0, rows, OW, C, bv.data_ptr(), cv.data_ptr(), kv, OH, _p(u8), _p(lut), _p(f32),
+              f32.stride(0) if f32 is not None else 0, f32.stride(1) if f32 is not None else 0, _stream())
+    return u8, f32
+
+
+def normalize_to_u8(x: torch.Tensor) -> torch.Tensor:
+    """((x - x.min()) / (x.max() - x.min() + 1e-8) * 255).astype(np.uint8) (app.py:190-191) with numpy's types: a uint16 tensor takes the difference
+    in uint16 and the quotient and product in float64; a float32 tensor does every step in float32.  -> uint8, same shape.  NaN inputs are out
+    of scope (numpy's min / max propagate them; the integer keys here do not)."""
+    kind = {torch.uint16: "u16", torch.float32: "f32"}.get(x.dtype)
+    if kind is None:
+        raise TypeError(f"normalize_to_u8 takes uint16 or float32, got {x.dtype}")
+    _chk(x, "x")
+    if x.numel() == 0:
+        raise ValueError("normalize_to_u8: empty input")
+    mm = torch.empty((2,), dtype=torch.int32, device=x.device)
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    _lib.call(f"ullsam_minmax_{kind}", x.data_ptr(), x.numel(), mm.data_ptr(), _stream())
+    _lib.call(f"ullsam_normalize_to_u8_{kind}", x.data_ptr(), x.numel(), mm.data_ptr(), out.data_ptr(), _stream())
     return out
