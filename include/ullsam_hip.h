@@ -443,6 +443,21 @@ int ullsam_minmax_f32(const float* x, long n, unsigned* mm, void* stream);      
 int ullsam_normalize_to_u8_u16(const unsigned short* x, long n, const unsigned* mm, unsigned char* out, void* stream);   /* app.py:190-191 */
 int ullsam_normalize_to_u8_f32(const float* x, long n, const unsigned* mm, unsigned char* out, void* stream);            /* app.py:226-228 */
 
+/* The interactive loop's display tail (csrc/interactive.hip; definitions in DESIGN.md "7b, continued: the interactive loop"): one pass over
+   the display image [H, W], which sits at (top, left) of the padded square of side `side` that the S x S model frame was resized from.
+   Replaces, per click, the 1024^2 F.interpolate + threshold (app.py:635-645), postprocess_mask's Image.NEAREST (app.py:283-287; with the
+   window, export_mask's resize-then-un-pad, app.py:807-820), save_instance's canvas write (app.py:692-707) and visualize_masks' blends
+   (app.py:748-772).  low f32 [P, LH, LW] logits; per display pixel: frame pixel f = min(((2 (d + off) + 1) S) / (2 side), S - 1) per axis,
+   v_p = the value ullsam_resize_bilinear gives at (fy, fx) of the [S, S] resize of low[p] (same bits), m_p = v_p > thr.
+   flags & 1 (paint): canvas = first_id + p for the last p with m_p (canvas i32 [H, W], updated in place; otherwise only read, may be NULL).
+   overlay u8 [H, W, 3] = image u8 [H, W, 3] through lut_inst[(id - 1) % K] (u8 [K, 3, 256]) where the canvas id > 0, then through lut_cur
+   (u8 [3, 256]) where flags & 2 (highlight) and m_{P-1}.  mask u8 [P, H, W].  stats i32 [P, 5] = area, x0, y0, x1, y1 of m_p (inclusive
+   maxima, zeros for an empty mask) with scratch i32 [5 P + 1].  mask, overlay and stats may each be NULL.  1 <= P <= 512. */
+int ullsam_click_finish(const float* low, int P, int LH, int LW, int S, int H, int W, int side, int top, int left, float thr,
+                        const unsigned char* image, int* canvas, int first_id, int flags, const unsigned char* lut_inst, int K,
+                        const unsigned char* lut_cur, unsigned char* mask, unsigned char* overlay, int* stats, int* scratch,
+                        void* stream);                        /* app.py:283-287, 635-645, 692-707, 748-772, 807-820 */
+
 /* fp8 (OCP e4m3) ViT path -- BASELINE.json configs[4]; the reference's bf16 encoder linears image_encoder.py:227,171-181 with
    8-bit operands: rows quantised with a per-row scale (optionally behind the block's LayerNorm :166,180), GEMM on the
    block-scaled fp8 MFMA, scales applied in the epilogue */

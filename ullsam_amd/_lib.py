@@ -109,6 +109,7 @@ SIGNATURES = {
     "ullsam_minmax_f32": [vp, i64, vp, vp],
     "ullsam_normalize_to_u8_u16": [vp, i64, vp, vp, vp],
     "ullsam_normalize_to_u8_f32": [vp, i64, vp, vp, vp],
+    "ullsam_click_finish": [vp] + [i32] * 9 + [f32, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp],
     "ullsam_rows_fp8": [vp, i32, i64, vp, i64, vp, vp, vp, i64, i32, f32, vp],
     "ullsam_gemm_fp8": [vp, i64, vp, vp, i64, vp, vp, i64, i32, vp, vp, i64, i32, i32, i32, i32, vp],
     "ullsam_rows_fp8_pow2": [vp, i32, i64, vp, i64, vp, i64, i32, vp],

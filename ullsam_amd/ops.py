@@ -888,6 +888,56 @@ def resize_nearest_i32(x: torch.Tensor, out_hw, window=None) -> torch.Tensor:
     return out
 
 
+# ---- the interactive loop's display tail (csrc/interactive.hip) ---------------------------------------------------------------------
+CLICK_MAX_P = 512
+
+
+def click_finish(low: torch.Tensor, frame: int, hw, side: Optional[int] = None, top: int = 0, left: int = 0, thr: float = 0.0,
+                 image: Optional[torch.Tensor] = None, canvas: Optional[torch.Tensor] = None, first_id: int = 1, paint: bool = False,
+                 highlight: bool = False, lut_inst: Optional[torch.Tensor] = None, lut_cur: Optional[torch.Tensor] = None,
+                 want_mask: bool = True, want_overlay: bool = False, want_stats: bool = True, mask: Optional[torch.Tensor] = None,
+                 overlay: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None):
+    """One launch from the logits low fp32 [P, LH, LW] of P masks to what the display shows (include/ullsam_hip.h ullsam_click_finish): the
+    display image is [H, W] = hw at (top, left) of the padded square of side `side` (default max(H, W)) that the frame x frame model input was
+    resized from.  Returns (mask uint8 [P, H, W], overlay uint8 [H, W, 3], stats int32 [P, 5] = area, x0, y0, x1, y1), None for what was not
+    asked for; mask= / overlay= / stats= are buffers to fill.  paint writes first_id + p into canvas int32 [H, W] in place (last p on top);
+    the overlay blends image uint8 [H, W, 3] through lut_inst uint8 [K, 3, 256] by canvas id and, with highlight, through lut_cur uint8 [3, 256]
+    where the last mask is set."""
+    _chk(low, "low", torch.float32)
+    assert low.dim() == 3, low.shape
+    P, LH, LW = low.shape
+    H, W = (int(v) for v in hw)
+    side = max(H, W) if side is None else int(side)
+    dev = low.device
+
+    def buf(t, want, shape, dtype, name):
+        if t is not None:
+            _chk(t, name, dtype)
+            assert tuple(t.shape) == shape, (name, tuple(t.shape), shape)
+            return t
+        return torch.empty(shape, dtype=dtype, device=dev) if want else None
+
+    mask = buf(mask, want_mask, (P, H, W), torch.uint8, "mask")
+    overlay = buf(overlay, want_overlay, (H, W, 3), torch.uint8, "overlay")
+    stats = buf(stats, want_stats, (P, 5), torch.int32, "stats")
+    K = 0
+    if overlay is not None:
+        if image is None or lut_inst is None or lut_cur is None:
+            raise _lib.UllsamError("click_finish: an overlay needs image, lut_inst and lut_cur")
+        _chk(image, "image", torch.uint8); _chk(lut_inst, "lut_inst", torch.uint8); _chk(lut_cur, "lut_cur", torch.uint8)
+        assert tuple(image.shape) == (H, W, 3) and lut_inst.dim() == 3 and tuple(lut_inst.shape[1:]) == (3, 256) and tuple(lut_cur.shape) == (3, 256)
+        K = int(lut_inst.shape[0])
+    if canvas is not None:
+        _chk(canvas, "canvas", torch.int32)
+        assert tuple(canvas.shape) == (H, W), (canvas.shape, (H, W))
+    scratch = torch.empty((5 * P + 1,), dtype=torch.int32, device=dev) if stats is not None else None
+    _lib.call("ullsam_click_finish", low.data_ptr(), P, LH, LW, int(frame), H, W, side, int(top), int(left), float(thr),
+              _p(image) if overlay is not None else None, _p(canvas), int(first_id), (1 if paint else 0) | (2 if highlight else 0),
+              _p(lut_inst) if overlay is not None else None, K, _p(lut_cur) if overlay is not None else None, _p(mask), _p(overlay),
+              _p(stats), _p(scratch), _stream())
+    return mask, overlay, stats
+
+
 # ---- prompts from an instance label image (csrc/prompts.hip) ----------------------------------------------------------------------
 PROMPT_MAX_ID = 65535
 PROMPT_MAX_RADIUS = 64
