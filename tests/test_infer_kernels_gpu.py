@@ -1,5 +1,5 @@
 """The inference kernels around the GEMM / ViT / causal / token-to-image attention / fused decoder kernels (those have their own tests in
-test_kernels_gpu.py), one by one, against float64 definitions of the reference's operations written here, at the shapes, dtypes, strides and
+test_kernels_gpu.py; the fused decoder kernels in test_decoder_kernels_gpu.py), one by one, against float64 definitions of the reference's operations written here, at the shapes, dtypes, strides and
 edges where their code paths divide: LLM data movement (csrc/llm_misc.hip), ViT / projector data movement (csrc/vit_misc.hip, csrc/norm.hip),
 the prompt encoder's and mask decoder's small kernels (csrc/decoder.hip, csrc/dectok.hip, csrc/amg.hip) and the edges of the small attention
 kernels (csrc/attention.hip: naive, few-keys, decode).
