@@ -390,6 +390,36 @@ int ullsam_label_remap(const int* raw, const int* map, long N, int H, int W, int
 int ullsam_label_overlap(const int* a, const int* b, int H, int W, int na, int nb, unsigned long long* T, int* status, void* stream);
 int ullsam_resize_nearest_i32(const int* in, long in_ld, int IH, int IW, int OH, int OW, int top, int left, int h, int w, int* out,
                               long out_ld, void* stream);                                     /* app.py:807-826, 145 reverse_padding */
+/* Tiled segment-everything: per-tile label maps stitched into one label image (csrc/mosaic.hip; integer work, bit-exact with the host form
+   utils.mosaic.stitch_label_maps; definition in DESIGN.md "7b, continued (mosaic)").  tiles i32 [T, th, tw], tile t with ids 0..K_t;
+   base i32 [T + 1] = the exclusive sum of the K_t, G = base[T] <= 2^31 - 2; the global id of (t, l > 0) is base[t] + l.  T <= 65535.
+   flags i32 [4]: [0] = 1 when an id lies outside 0..K_t (it reads as background) or a descriptor leaves its tile / the frame (it is not
+   walked), [1] = 1 when the pair table refused a key, [2] = the number of distinct pairs; ([3] is free for K).
+   mosaic_seams: seams i32 [S, 9] = (s, t, sy, sx, ty, tx, h, w, dir): the intersection of the boxes of tile s and its right (dir 0) or lower
+     (dir 1) neighbour t, as an h x w window at (sy, sx) of s and (ty, tx) of t; max_rows = the largest h.  Zeroes its outputs, then counts
+     areas i32 [G + 1, 4]: areas[g, c] = the pixels of g inside the seam on side c of its tile (0 left, 1 right, 2 up, 3 down), and the
+     pairs: keys u64 [cap] (dir << 63 | g_a << 32 | g_b, 0 = empty slot, open addressing), counts i32 [cap] = #{p : s(p) = a, t(p) = b},
+     a, b > 0.  cap a power of two >= 2 * max_pairs; more than max_pairs distinct pairs set flags[1] / show in flags[2].
+   mosaic_union: parent i32 [G + 1] = the smallest global id of the component of g in the graph of the merged pairs; a pair of the table
+     merges when n > 0 and n * den >= num * (A_s(a) + A_t(b) - n) (64-bit; 0 < num <= den < 2^31), every pair when areas is NULL
+     (counts is not read then, and cap is any length).
+   mosaic_stats: cores i32 [T, 6] = (top, left, h, w of the tile's core in the [H, W] frame, then the tile's origin oy, ox); max_rows = the
+     largest h.  areas_raw i32 [G + 1], boxes_raw i32 [G + 1, 4] (inclusive XYXY) of the core pixels per REPRESENTATIVE; others keep area 0
+     and the box INT_MAX, INT_MAX, -1, -1.
+   mosaic_compact: a representative is dropped when its area is 0 or < min_visible_area, the others are renumbered 1..K by ascending id:
+     label_of_global i32 [G + 1] (0 = dropped, members follow their representative), areas i32 [G] / boxes i32 [G, 4] (first K entries), K i32 [1].
+   mosaic_paste: labels i32 [H, W][p] = label_of_global[base[t] + tile_t[p - origin_t]] for p in the core of t (0 where the tile says 0);
+     the cores partition the frame, so every pixel is written once; the frame is indexed in 64 bits. */
+int ullsam_mosaic_seams(const int* tiles, int T, int th, int tw, const int* base, long G, const int* seams, int S, int max_rows,
+                        unsigned long long* keys, int* counts, long cap, int max_pairs, int* areas, int* flags, void* stream);
+int ullsam_mosaic_union(const unsigned long long* keys, const int* counts, long cap, const int* areas, long G, long num, long den, int* parent,
+                        int* flags, void* stream);
+int ullsam_mosaic_stats(const int* tiles, int T, int th, int tw, const int* base, long G, const int* cores, int max_rows, const int* parent,
+                        int H, int W, int* areas_raw, int* boxes_raw, int* flags, void* stream);
+int ullsam_mosaic_compact(const int* areas_raw, const int* boxes_raw, const int* parent, long G, int min_visible_area, int* label_of_global,
+                          int* areas, int* boxes, int* K, void* stream);
+int ullsam_mosaic_paste(const int* tiles, int T, int th, int tw, const int* base, long G, const int* cores, int max_rows,
+                        const int* label_of_global, int H, int W, int* labels, void* stream);
 
 /* Point prompts, boxes and per-instance masks from one instance label image (csrc/prompts.hip; the reference's dataset loop
    train_joint_v2.py:313-468 as integer kernels, bit-exact with utils.prompts' host route; definitions in DESIGN.md "7b, continued (prompts)").

@@ -425,3 +425,42 @@ class SamAutomaticMaskGenerator:
         if out_hw is not None or window is not None:
             labels = A.resize_labels_nearest(labels, tuple(labels.shape) if out_hw is None else out_hw, window)
         return labels, records
+
+    @torch.no_grad()
+    def generate_tiled_label_map(self, image, tile: int = 2048, overlap: int = 256, order: str = "area", min_visible_area: int = 0, iou=(1, 2)):
+        """Segment everything on a frame far larger than the model's input (a slide, a well scan): the frame is cut into the overlapping tiles of
+        utils.mosaic.tile_grid(H, W, tile, overlap), every tile goes through generate_label_map(image[window], order=order) at its native
+        resolution, its label map stays on the device, and utils.mosaic.stitch_label_maps (csrc/mosaic.hip) merges the instances across the seams
+        -- two tiles' labels are one instance when their IoU inside the seam is at least iou = (num, den) -- into ONE label image.
+        image: H x W x 3 on the host (numpy or tensor, the dtypes of generate()).  -> (labels int32 [H, W] on the model's device, records): the
+        tiles' records concatenated in tile order, each with "tile" (its tile's index), "offset" (the tile's (top, left); "bbox", "point_coords"
+        and the RLE stay in tile coordinates) and "label" = its id in the MOSAIC (0: hidden in its tile, owned by a neighbour's core and not
+        merged with anything visible, or dropped).  min_visible_area is applied once, to the stitched instances, not per tile.
+        Not done here: tiles are not sharded over ranks (one process walks them all), the whole image has to fit in host memory, diagonal
+        neighbours have no seam of their own (they merge through the tile between them), and the model is not run again on the seam regions."""
+        from .utils import mosaic as M
+        if isinstance(image, torch.Tensor):
+            image = image.detach().cpu().numpy()
+        image = np.asarray(image)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError(f"generate_tiled_label_map: the image must be H x W x 3, got {tuple(image.shape)}")
+        grid = M.tile_grid(image.shape[0], image.shape[1], tile, overlap)
+        dev = self.model.device
+        tiles = torch.empty((grid.ntiles, grid.th, grid.tw), dtype=torch.int32, device=dev)
+        records, counts = [], []
+        for t, (top, left, h, w) in enumerate(grid.boxes()):
+            labels_t, recs = self.generate_label_map(image[top:top + h, left:left + w], order=order)
+            tiles[t].copy_(labels_t)
+            counts.append(max((r["label"] for r in recs), default=0))            # the tile's labels are 1..K_t
+            for r in recs:
+                r["tile"], r["offset"] = t, (top, left)
+            records.append(recs)
+        labels, label_of_global, _, _ = M.stitch_label_maps(tiles, counts, grid, iou=iou, min_visible_area=min_visible_area, device=dev)
+        lut = label_of_global.cpu().numpy()
+        base = np.concatenate([[0], np.cumsum(counts)])
+        out = []
+        for t, recs in enumerate(records):
+            for r in recs:
+                r["label"] = int(lut[base[t] + r["label"]]) if r["label"] else 0
+                out.append(r)
+        return labels, out

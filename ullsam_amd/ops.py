@@ -888,6 +888,105 @@ def resize_nearest_i32(x: torch.Tensor, out_hw, window=None) -> torch.Tensor:
     return out
 
 
+# ---- per-tile label maps stitched into one label image (csrc/mosaic.hip; utils.mosaic drives these) -----------------------------------------
+MOSAIC_MAX_TILES = 65535
+MOSAIC_MAX_IDS = 2 ** 31 - 2
+MOSAIC_FLAGS = 4          # bad id / descriptor, table overflow, distinct pairs, (free: utils.mosaic keeps K there)
+
+
+def mosaic_table_slots(max_pairs: int) -> int:
+    """The pair table's capacity: the power of two >= 2 * max_pairs."""
+    return 1 << max(1, (2 * int(max_pairs) - 1).bit_length())
+
+
+def _mosaic_tiles(tiles: torch.Tensor, base: torch.Tensor):
+    _chk(tiles, "tiles", torch.int32); _chk(base, "base", torch.int32)
+    assert tiles.dim() == 3 and base.numel() == tiles.shape[0] + 1, (tuple(tiles.shape), base.numel())
+    t, th, tw = tiles.shape
+    if not (1 <= t <= MOSAIC_MAX_TILES and th > 0 and tw > 0):
+        raise _lib.UllsamError(f"mosaic: tiles {tuple(tiles.shape)} must be [1..{MOSAIC_MAX_TILES}, th > 0, tw > 0]")
+    return t, th, tw
+
+
+def mosaic_seams(tiles: torch.Tensor, base: torch.Tensor, g: int, seams: torch.Tensor, max_rows: int, max_pairs: int,
+                 flags: Optional[torch.Tensor] = None):
+    """tiles int32 [T, th, tw], base int32 [T + 1] (exclusive sum of the tiles' id counts, g = base[T]), seams int32 [S, 9] (ullsam_hip.h) ->
+    (keys int64 [slots] -- dir << 63 | g_a << 32 | g_b, 0 = empty --, counts int32 [slots], areas int32 [g + 1, 4], flags int32 [4]); the caller reads flags."""
+    t, th, tw = _mosaic_tiles(tiles, base)
+    _chk(seams, "seams", torch.int32)
+    assert seams.dim() == 2 and seams.shape[1] == 9 and 0 <= g <= MOSAIC_MAX_IDS and max_pairs >= 1
+    dev = tiles.device
+    cap = mosaic_table_slots(max_pairs)
+    keys = torch.empty((cap,), dtype=torch.int64, device=dev)
+    counts = torch.empty((cap,), dtype=torch.int32, device=dev)
+    areas = torch.empty((g + 1, 4), dtype=torch.int32, device=dev)
+    flags = _out_i32(flags, (MOSAIC_FLAGS,), dev, "flags")
+    _lib.call("ullsam_mosaic_seams", tiles.data_ptr(), t, th, tw, base.data_ptr(), g, seams.data_ptr(), seams.shape[0], int(max_rows), keys.data_ptr(),
+              counts.data_ptr(), cap, int(max_pairs), areas.data_ptr(), flags.data_ptr(), _stream())
+    return keys, counts, areas, flags
+
+
+def mosaic_union(keys: torch.Tensor, g: int, counts: Optional[torch.Tensor] = None, areas: Optional[torch.Tensor] = None, iou=(1, 2),
+                 flags: Optional[torch.Tensor] = None):
+    """Pair keys int64 [n] (0 = none) over the ids 1..g -> (parent int32 [g + 1]: the smallest id of every id's component, flags).  With counts / areas
+    (mosaic_seams' outputs) a pair merges when n > 0 and n * den >= num * (A_s + A_t - n), iou = (num, den); without them every pair merges."""
+    _chk(keys, "keys", torch.int64)
+    assert (counts is None) == (areas is None)
+    if areas is not None:
+        _chk(counts, "counts", torch.int32); _chk(areas, "areas", torch.int32)
+        assert counts.numel() == keys.numel() and areas.numel() == 4 * (g + 1)
+    num, den = (int(v) for v in iou)
+    if not (0 < num <= den < 2 ** 31):
+        raise _lib.UllsamError(f"mosaic_union: iou = (num, den) needs 0 < num <= den < 2^31, got {(num, den)}")
+    parent = torch.empty((g + 1,), dtype=torch.int32, device=keys.device)
+    flags = torch.zeros((MOSAIC_FLAGS,), dtype=torch.int32, device=keys.device) if flags is None else _out_i32(flags, (MOSAIC_FLAGS,), keys.device, "flags")
+    _lib.call("ullsam_mosaic_union", keys.data_ptr(), _p(counts), keys.numel(), _p(areas), g, num, den, parent.data_ptr(), flags.data_ptr(), _stream())
+    return parent, flags
+
+
+def mosaic_stats(tiles: torch.Tensor, base: torch.Tensor, g: int, cores: torch.Tensor, max_rows: int, parent: torch.Tensor, h: int, w: int,
+                 flags: Optional[torch.Tensor] = None):
+    """cores int32 [T, 6] (ullsam_hip.h), parent as mosaic_union leaves it -> (areas_raw int32 [g + 1], boxes_raw int32 [g + 1, 4] inclusive XYXY) of the core
+    pixels per representative."""
+    t, th, tw = _mosaic_tiles(tiles, base)
+    _chk(cores, "cores", torch.int32); _chk(parent, "parent", torch.int32)
+    assert tuple(cores.shape) == (t, 6) and parent.numel() == g + 1
+    dev = tiles.device
+    areas = torch.empty((g + 1,), dtype=torch.int32, device=dev)
+    boxes = torch.empty((g + 1, 4), dtype=torch.int32, device=dev)
+    flags = torch.zeros((MOSAIC_FLAGS,), dtype=torch.int32, device=dev) if flags is None else _out_i32(flags, (MOSAIC_FLAGS,), dev, "flags")
+    _lib.call("ullsam_mosaic_stats", tiles.data_ptr(), t, th, tw, base.data_ptr(), g, cores.data_ptr(), int(max_rows), parent.data_ptr(), int(h), int(w),
+              areas.data_ptr(), boxes.data_ptr(), flags.data_ptr(), _stream())
+    return areas, boxes, flags
+
+
+def mosaic_compact(areas_raw: torch.Tensor, boxes_raw: torch.Tensor, parent: torch.Tensor, min_visible_area: int = 0, k_out: Optional[torch.Tensor] = None):
+    """-> (label_of_global int32 [g + 1], areas int32 [g], boxes int32 [g, 4] -- their first K entries are the final labels' --, K int32 [1])."""
+    _chk(areas_raw, "areas_raw", torch.int32); _chk(boxes_raw, "boxes_raw", torch.int32); _chk(parent, "parent", torch.int32)
+    g = parent.numel() - 1
+    assert g >= 0 and areas_raw.numel() == g + 1 and boxes_raw.numel() == 4 * (g + 1)
+    dev = parent.device
+    log = torch.empty((g + 1,), dtype=torch.int32, device=dev)
+    areas = torch.zeros((g,), dtype=torch.int32, device=dev)
+    boxes = torch.zeros((g, 4), dtype=torch.int32, device=dev)
+    k_out = _out_i32(k_out, (1,), dev, "k_out")
+    _lib.call("ullsam_mosaic_compact", areas_raw.data_ptr(), boxes_raw.data_ptr(), parent.data_ptr(), g, int(min_visible_area), log.data_ptr(),
+              areas.data_ptr(), boxes.data_ptr(), k_out.data_ptr(), _stream())
+    return log, areas, boxes, k_out
+
+
+def mosaic_paste(tiles: torch.Tensor, base: torch.Tensor, g: int, cores: torch.Tensor, max_rows: int, label_of_global: torch.Tensor, h: int, w: int,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """labels int32 [h, w]: every tile's core copied through label_of_global (the cores must partition the frame: nothing else is written)."""
+    t, th, tw = _mosaic_tiles(tiles, base)
+    _chk(cores, "cores", torch.int32); _chk(label_of_global, "label_of_global", torch.int32)
+    assert tuple(cores.shape) == (t, 6) and label_of_global.numel() == g + 1
+    out = _out_i32(out, (int(h), int(w)), tiles.device, "out")
+    _lib.call("ullsam_mosaic_paste", tiles.data_ptr(), t, th, tw, base.data_ptr(), g, cores.data_ptr(), int(max_rows), label_of_global.data_ptr(),
+              int(h), int(w), out.data_ptr(), _stream())
+    return out
+
+
 # ---- the interactive loop's display tail (csrc/interactive.hip) ---------------------------------------------------------------------
 CLICK_MAX_P = 512
 

@@ -61,6 +61,27 @@ def label_tile(seed: int, size: int = 1024, n_cells: int = 14, r_range: Tuple[fl
     return labels
 
 
+def label_frame(seed: int, height: int, width: int, n_cells: int, r_range: Tuple[float, float] = (70.0, 150.0)) -> np.ndarray:
+    """label_tile for a frame too large to test every disc against every pixel (a mosaic of tiles): the same draws -- centres uniform over
+    max(height, width), so a square frame gets label_tile's image exactly -- and the same float32 disc test, evaluated inside each disc's bounding
+    box only.  -> int32 [height, width], cell i carries id i + 1, later cells on top."""
+    size = max(height, width)
+    rng = np.random.default_rng([int(seed), 0x5EED])
+    cx = rng.uniform(0, size, n_cells)
+    cy = rng.uniform(0, size, n_cells)
+    r = rng.uniform(r_range[0], r_range[1], n_cells)
+    labels = np.zeros((height, width), np.int32)
+    for i in range(n_cells):
+        y0, y1 = max(int(cy[i] - r[i]) - 1, 0), min(int(cy[i] + r[i]) + 2, height)
+        x0, x1 = max(int(cx[i] - r[i]) - 1, 0), min(int(cx[i] + r[i]) + 2, width)
+        if y0 >= y1 or x0 >= x1:
+            continue
+        yy, xx = np.mgrid[y0:y1, x0:x1].astype(np.float32)
+        disc = (xx - np.float32(cx[i])) ** 2 + (yy - np.float32(cy[i])) ** 2 < np.float32(r[i]) ** 2
+        labels[y0:y1, x0:x1][disc] = i + 1
+    return labels
+
+
 def param_init_rule(name: str, shape) -> Tuple[float, float]:
     """(mean, std) of the normal distribution bench.py draws parameter `name` from: the same per-name table the reference-generated
     fixtures were filled with (oracle/ullsam_oracle.py::fill_param; tests/test_host_cpu.py checks the two agree), so the bench runs on
