@@ -420,6 +420,27 @@ int ullsam_mosaic_compact(const int* areas_raw, const int* boxes_raw, const int*
                           int* areas, int* boxes, int* K, void* stream);
 int ullsam_mosaic_paste(const int* tiles, int T, int th, int tw, const int* base, long G, const int* cores, int max_rows,
                         const int* label_of_global, int H, int W, int* labels, void* stream);
+/* Per-instance measurements and contacts from a label image (csrc/measure.hip; integer work, bit-exact with the host forms
+   utils.measure.measure_instances / label_contacts; definition in DESIGN.md "7b, continued: measurements").  labels i32 [H, W] with ids
+   0..K, 0 = background, 1 <= H, W <= 46340 (x * x and every area stay below 2^31, every sum below 2^62), K <= 2^31 - 2.  Row k - 1 of every
+   table belongs to label k; both entries set all of their outputs themselves (init kernels), the caller zeroes nothing.
+   flags i32 [4]: [0] = 1 when an id lies outside 0..K (it reads as background; no table is indexed with it), [1] = 1 when the pair table
+   refused a key, [2] = the number of distinct pairs, [3] = the number of rows label_contacts wrote.
+   measure_instances: area i64 [K]; box i32 [K, 4] inclusive XYXY, (INT_MAX, INT_MAX, -1, -1) for an absent label; moments i64 [K, 5] = sum x,
+     sum y, sum x^2, sum y^2, sum xy in frame coordinates; perimeter i64 [K, 3] = boundary pixels (pixels of k with a 4-neighbour that is not
+     k), edges (pixel sides of k facing "not k"), contact edges (those facing another instance); the frame's outside is "not k" and is no
+     instance.  intensity: NULL with channels = 0, else u8 (sample_bytes 1) or u16 (2) interleaved [H, W, channels], channels <= 4, any
+     element-aligned address: isum / isum2 i64 [K, channels] = sum v, sum v^2; imin / imax i32 [K, channels], (INT_MAX, -1) for an absent label.
+     lds_slots: the entries of the per-workgroup LDS table the runs are summed in before one global atomic per quantity and label (0 or a
+     power of two <= 128; 0 = every run straight to the global tables; the results are the same).
+   label_contacts: keys u64 [cap] / counts i64 [cap]: the open-addressing pair table (key a << 32 | b, 0 < a < b; cap a power of two
+     >= 2 * max_pairs), counts = the pixel sides shared by a pixel of a and a 4-neighbour pixel of b, every adjacent pixel pair counted once
+     (right and down); rows i64 [max_pairs, 2] = (key, n) of the claimed slots in no particular order, flags[3] of them. */
+int ullsam_measure_instances(const int* labels, int H, int W, int K, const void* intensity, int channels, int sample_bytes, int lds_slots,
+                             long* area, int* box, long* moments, long* perimeter, long* isum, long* isum2, int* imin, int* imax, int* flags,
+                             void* stream);
+int ullsam_label_contacts(const int* labels, int H, int W, int K, unsigned long long* keys, long* counts, long cap, int max_pairs, long* rows,
+                          int* flags, void* stream);
 
 /* Point prompts, boxes and per-instance masks from one instance label image (csrc/prompts.hip; the reference's dataset loop
    train_joint_v2.py:313-468 as integer kernels, bit-exact with utils.prompts' host route; definitions in DESIGN.md "7b, continued (prompts)").

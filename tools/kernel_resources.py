@@ -40,7 +40,9 @@ HOT_DECODE_FP8 = [r"rows_fp8_pow2_kernel", r"gemm_skinny_kernelILi\d+ELb[01]ELb1
 # instance label maps and their overlap table (csrc/labels.hip): paint, stats, compaction, remap + transpose, overlap, nearest resize
 HOT_LABELS = [r"rle_paint_kernel", r"label_stats_init_kernel", r"label_stats_kernel", r"label_compact_kernel", r"label_remap_kernel", r"label_overlap_kernel",
               r"resize_nearest_i32_kernel"]
-HOT_BF16 = HOT_BF16 + HOT_AMG + HOT_REGIONS + HOT_DECODE_FP8 + HOT_LABELS
+# per-instance measurements and contacts from a label image (csrc/measure.hip)
+HOT_MEASURE = [r"measure_kernelILi\dE", r"contacts_kernel"]
+HOT_BF16 = HOT_BF16 + HOT_AMG + HOT_REGIONS + HOT_DECODE_FP8 + HOT_LABELS + HOT_MEASURE
 HOT = HOT_BF16
 # round 6: the persistent ring kernel in its default schedule (SCHED 2, no stamps, no ablation): no spilled VECTOR register and no scratch.  Its tile loop keeps more scalars than the 102 SGPRs hold
 # (tile coordinates, two buffer descriptors, the kernel arguments the epilogue reads): hipcc parks the overflow in lanes of a VGPR (v_writelane / v_readlane, outside the K loop) -- counted as

@@ -103,6 +103,8 @@ SIGNATURES = {
     "ullsam_mosaic_stats": [vp, i32, i32, i32, vp, i64, vp, i32, vp, i32, i32, vp, vp, vp, vp],
     "ullsam_mosaic_compact": [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp],
     "ullsam_mosaic_paste": [vp, i32, i32, i32, vp, i64, vp, i32, vp, i32, i32, vp, vp],
+    "ullsam_measure_instances": [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "ullsam_label_contacts": [vp, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp],
     "ullsam_label_d1": [vp, i32, i32, i32, vp, vp, vp, vp],
     "ullsam_prompt_choose": [vp, i32, C.c_ulonglong, vp, vp, vp, vp, vp],
     "ullsam_prompt_sets": [vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],

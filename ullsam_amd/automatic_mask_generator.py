@@ -34,6 +34,13 @@ from . import ops
 from .utils import amg as A
 
 
+def _measure_image_check(image, what: str) -> None:
+    dt = str(getattr(image, "dtype", None)).replace("torch.", "")
+    shape = tuple(getattr(image, "shape", ()))
+    if dt != "uint8" or len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"{what}: measure=True needs an H x W x 3 uint8 image, got {dt} {shape}")
+
+
 class SamAutomaticMaskGenerator:
     def __init__(self, model, points_per_side: Optional[int] = 32, points_per_batch: int = 64, pred_iou_thresh: float = 0.88,
                  stability_score_thresh: float = 0.95, stability_score_offset: float = 1.0, box_nms_thresh: float = 0.7,
@@ -407,27 +414,37 @@ class SamAutomaticMaskGenerator:
         return self._records(self._generate_data(image)[0], self.output_mode)
 
     @torch.no_grad()
-    def generate_label_map(self, image, order: str = "area", min_visible_area: int = 0, out_hw=None, window=None):
+    def generate_label_map(self, image, order: str = "area", min_visible_area: int = 0, out_hw=None, window=None, measure: bool = False):
         """Segment everything, then paint the records into ONE instance label image -- the file the app exports (app.py:688-707 save_instance,
         :807-826 export_mask) -- on the device (utils.amg.paint_label_map; csrc/labels.hip).  -> (labels int32 [H, W] on the model's device,
         records): the records are those of generate() with output_mode="uncompressed_rle", in the same order, each with one more key "label" = its
         id in `labels` (0: the record is fully covered by records painted after it, or keeps fewer than `min_visible_area` visible pixels).
         order: "area" (default; large first, so small objects stay on top), "score" (ascending predicted_iou) or "record" (list order, the app's).
         out_hw / window = (top, left, h, w): nearest resize of the label image and the part of it to return (the app's export resize and
-        reverse_padding; utils.amg.resize_labels_nearest)."""
+        reverse_padding; utils.amg.resize_labels_nearest).
+        measure=True: a third value, the utils.measure.InstanceTable of `labels` against the image, which must then be H x W x 3 uint8 (it is
+        uploaded once more, at 1 byte per sample); not with out_hw / window, after which the labels are no longer in the image's frame."""
+        if measure:
+            if out_hw is not None or window is not None:
+                raise ValueError("generate_label_map: measure=True needs the labels in the image's frame (no out_hw / window)")
+            _measure_image_check(image, "generate_label_map")
         data, orig_size = self._generate_data(image)
         records = self._records(data, "uncompressed_rle")
         keys = [r["predicted_iou"] for r in records] if order == "score" else None
-        labels, of_record, _, _ = A.paint_label_map([r["segmentation"] for r in records], order=order, keys=keys, min_visible_area=min_visible_area,
+        labels, of_record, areas, _ = A.paint_label_map([r["segmentation"] for r in records], order=order, keys=keys, min_visible_area=min_visible_area,
                                                     device=self.model.device, size=orig_size)
         for r, l in zip(records, of_record.cpu().tolist()):
             r["label"] = int(l)
         if out_hw is not None or window is not None:
             labels = A.resize_labels_nearest(labels, tuple(labels.shape) if out_hw is None else out_hw, window)
+        if measure:
+            from .utils import measure as MS
+            return labels, records, MS.measure_instances(labels, torch.as_tensor(image), num=len(areas), device=labels.device)
         return labels, records
 
     @torch.no_grad()
-    def generate_tiled_label_map(self, image, tile: int = 2048, overlap: int = 256, order: str = "area", min_visible_area: int = 0, iou=(1, 2)):
+    def generate_tiled_label_map(self, image, tile: int = 2048, overlap: int = 256, order: str = "area", min_visible_area: int = 0, iou=(1, 2),
+                                 measure: bool = False):
         """Segment everything on a frame far larger than the model's input (a slide, a well scan): the frame is cut into the overlapping tiles of
         utils.mosaic.tile_grid(H, W, tile, overlap), every tile goes through generate_label_map(image[window], order=order) at its native
         resolution, its label map stays on the device, and utils.mosaic.stitch_label_maps (csrc/mosaic.hip) merges the instances across the seams
@@ -436,6 +453,8 @@ class SamAutomaticMaskGenerator:
         tiles' records concatenated in tile order, each with "tile" (its tile's index), "offset" (the tile's (top, left); "bbox", "point_coords"
         and the RLE stay in tile coordinates) and "label" = its id in the MOSAIC (0: hidden in its tile, owned by a neighbour's core and not
         merged with anything visible, or dropped).  min_visible_area is applied once, to the stitched instances, not per tile.
+        measure=True: a third value, the utils.measure.InstanceTable of the stitched labels against the image, which must then be uint8 (it is
+        uploaded once, at 1 byte per sample).
         Not done here: tiles are not sharded over ranks (one process walks them all), the whole image has to fit in host memory, diagonal
         neighbours have no seam of their own (they merge through the tile between them), and the model is not run again on the seam regions."""
         from .utils import mosaic as M
@@ -444,6 +463,8 @@ class SamAutomaticMaskGenerator:
         image = np.asarray(image)
         if image.ndim != 3 or image.shape[2] != 3:
             raise ValueError(f"generate_tiled_label_map: the image must be H x W x 3, got {tuple(image.shape)}")
+        if measure:
+            _measure_image_check(image, "generate_tiled_label_map")
         grid = M.tile_grid(image.shape[0], image.shape[1], tile, overlap)
         dev = self.model.device
         tiles = torch.empty((grid.ntiles, grid.th, grid.tw), dtype=torch.int32, device=dev)
@@ -455,7 +476,7 @@ class SamAutomaticMaskGenerator:
             for r in recs:
                 r["tile"], r["offset"] = t, (top, left)
             records.append(recs)
-        labels, label_of_global, _, _ = M.stitch_label_maps(tiles, counts, grid, iou=iou, min_visible_area=min_visible_area, device=dev)
+        labels, label_of_global, areas, _ = M.stitch_label_maps(tiles, counts, grid, iou=iou, min_visible_area=min_visible_area, device=dev)
         lut = label_of_global.cpu().numpy()
         base = np.concatenate([[0], np.cumsum(counts)])
         out = []
@@ -463,4 +484,7 @@ class SamAutomaticMaskGenerator:
             for r in recs:
                 r["label"] = int(lut[base[t] + r["label"]]) if r["label"] else 0
                 out.append(r)
+        if measure:
+            from .utils import measure as MS
+            return labels, out, MS.measure_instances(labels, torch.from_numpy(np.ascontiguousarray(image)), num=len(areas), device=dev)
         return labels, out

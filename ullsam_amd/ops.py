@@ -987,6 +987,87 @@ def mosaic_paste(tiles: torch.Tensor, base: torch.Tensor, g: int, cores: torch.T
     return out
 
 
+# ---- per-instance measurements and contacts from a label image (csrc/measure.hip; utils.measure drives these) ---------------------------------
+MEASURE_MAX_SIDE = 46340  # x * x < 2^31 and H * W < 2^31: every sum of the tables stays below 2^62
+MEASURE_MAX_CHANNELS = 4
+MEASURE_LDS_SLOTS = 128   # the per-workgroup LDS table of the default route, and the largest (0: every run straight to the global tables)
+MEASURE_FLAGS = 4         # bad id, pair table overflow, distinct pairs, rows written
+
+
+def _measure_frame(labels: torch.Tensor, num: int, what: str):
+    _chk(labels, "labels", torch.int32)
+    if labels.dim() != 2:
+        raise ValueError(f"{what}: labels must be [H, W], got {tuple(labels.shape)}")
+    h, w = labels.shape
+    if not (1 <= h <= MEASURE_MAX_SIDE and 1 <= w <= MEASURE_MAX_SIDE):
+        raise _lib.UllsamError(f"{what}: a frame of {h} x {w} (each side must lie in 1..{MEASURE_MAX_SIDE})")
+    if not 0 <= int(num) <= MOSAIC_MAX_IDS:
+        raise _lib.UllsamError(f"{what}: num = {num} must lie in 0..2^31 - 2")
+    return h, w
+
+
+def _out_view(out, name: str, shape, dtype, device) -> torch.Tensor:
+    if out is None or name not in out:
+        return torch.empty(shape, dtype=dtype, device=device)
+    t = out[name]
+    _chk(t, name, dtype)
+    assert tuple(t.shape) == tuple(shape), (name, tuple(t.shape), tuple(shape))
+    return t
+
+
+def measure_instances(labels: torch.Tensor, num: int, intensity: Optional[torch.Tensor] = None, lds_slots: int = MEASURE_LDS_SLOTS,
+                      out: Optional[dict] = None, flags: Optional[torch.Tensor] = None):
+    """labels int32 [H, W] with ids 0..num, intensity None or uint8 / uint16 [H, W] / [H, W, C <= 4] -> (dict of the tables of ullsam_hip.h: area int64
+    [num], box int32 [num, 4], moments int64 [num, 5], perimeter int64 [num, 3] and, with an image, isum / isum2 int64 [num, C], imin / imax int32
+    [num, C]; flags int32 [4]: the caller reads flags[0]).  lds_slots: a power of two <= 128 (the runs of equal labels are summed in a per-workgroup LDS
+    table first: the faster route as measured, tools/measure_bench.py) or 0 (every run straight to the global tables); same results.  out: preallocated tables by name."""
+    h, w = _measure_frame(labels, num, "measure_instances")
+    k, dev = int(num), labels.device
+    c, nbytes = 0, 0
+    if intensity is not None:
+        if intensity.dtype not in (torch.uint8, torch.uint16):
+            raise _lib.UllsamError(f"measure_instances: the intensity image must be uint8 or uint16, got {intensity.dtype} (float sums depend on the order of arrival)")
+        _chk(intensity, "intensity")
+        if intensity.dim() not in (2, 3) or tuple(intensity.shape[:2]) != (h, w):
+            raise ValueError(f"measure_instances: intensity {tuple(intensity.shape)} for labels {(h, w)}")
+        c = 1 if intensity.dim() == 2 else int(intensity.shape[2])
+        if not 1 <= c <= MEASURE_MAX_CHANNELS:
+            raise _lib.UllsamError(f"measure_instances: {c} channels (1..{MEASURE_MAX_CHANNELS})")
+        nbytes = intensity.element_size()
+    lds_slots = int(lds_slots)
+    if lds_slots < 0 or lds_slots > MEASURE_LDS_SLOTS or lds_slots & (lds_slots - 1):
+        raise _lib.UllsamError(f"measure_instances: lds_slots = {lds_slots} must be 0 or a power of two <= {MEASURE_LDS_SLOTS}")
+    i32, i64 = torch.int32, torch.int64
+    t = {"area": _out_view(out, "area", (k,), i64, dev), "box": _out_view(out, "box", (k, 4), i32, dev),
+         "moments": _out_view(out, "moments", (k, 5), i64, dev), "perimeter": _out_view(out, "perimeter", (k, 3), i64, dev)}
+    if c:
+        t.update(isum=_out_view(out, "isum", (k, c), i64, dev), isum2=_out_view(out, "isum2", (k, c), i64, dev),
+                 imin=_out_view(out, "imin", (k, c), i32, dev), imax=_out_view(out, "imax", (k, c), i32, dev))
+    flags = _out_i32(flags, (MEASURE_FLAGS,), dev, "flags")
+    _lib.call("ullsam_measure_instances", labels.data_ptr(), h, w, k, _p(intensity), c, nbytes, lds_slots, t["area"].data_ptr(), t["box"].data_ptr(),
+              t["moments"].data_ptr(), t["perimeter"].data_ptr(), _p(t.get("isum")), _p(t.get("isum2")), _p(t.get("imin")), _p(t.get("imax")),
+              flags.data_ptr(), _stream())
+    return t, flags
+
+
+def label_contacts(labels: torch.Tensor, num: int, max_pairs: int = 1 << 20, flags: Optional[torch.Tensor] = None):
+    """labels int32 [H, W] with ids 0..num -> (rows int64 [max_pairs, 2] = (a << 32 | b, n) of the pairs 0 < a < b that share n pixel sides, in no
+    particular order; flags int32 [4]: bad id, overflow, distinct pairs, rows written -- the caller reads them and keeps the first flags[2] rows)."""
+    h, w = _measure_frame(labels, num, "label_contacts")
+    max_pairs = int(max_pairs)
+    if not 1 <= max_pairs <= 2 ** 30:
+        raise _lib.UllsamError(f"label_contacts: max_pairs must lie in 1..2^30, got {max_pairs}")
+    dev = labels.device
+    cap = mosaic_table_slots(max_pairs)
+    keys = torch.empty((cap,), dtype=torch.int64, device=dev)
+    counts = torch.empty((cap,), dtype=torch.int64, device=dev)
+    rows = torch.empty((max_pairs, 2), dtype=torch.int64, device=dev)
+    flags = _out_i32(flags, (MEASURE_FLAGS,), dev, "flags")
+    _lib.call("ullsam_label_contacts", labels.data_ptr(), h, w, int(num), keys.data_ptr(), counts.data_ptr(), cap, max_pairs, rows.data_ptr(),
+              flags.data_ptr(), _stream())
+    return rows, flags
+
+
 # ---- the interactive loop's display tail (csrc/interactive.hip) ---------------------------------------------------------------------
 CLICK_MAX_P = 512
 
