@@ -43,6 +43,11 @@ def test_c_abi_exports_every_declared_symbol(lib):
     # the measurement knobs are host-side state: settable without a GPU, and an unknown key is an error with a message, not a crash
     assert lib.ullsam_set_gemm_tuning(1, 7) == 0 and lib.ullsam_set_gemm_tuning(0, 4) == 0
     assert lib.ullsam_set_gemm_tuning(99, 0) != 0 and b"unknown key" in lib.ullsam_last_error_string()
+    # key 2 (how multi-round ring launches run): one tile per workgroup or THE persistent schedule, nothing else
+    assert lib.ullsam_set_gemm_tuning(2, 0) == 0 and lib.ullsam_set_gemm_tuning(2, 2) == 0
+    for v in (1, 3, 4, 5, 6, 7):
+        assert lib.ullsam_set_gemm_tuning(2, v) != 0 and b"bad value %d" % v in lib.ullsam_last_error_string(), v
+    assert lib.ullsam_set_gemm_tuning(2, 2) == 0   # the default again
 
 
 def test_c_abi_argument_counts_match_header():
@@ -514,7 +519,7 @@ def test_hot_kernels_compile_without_spills():
            if r.get("vgpr_spill_count", 0) or r.get("sgpr_spill_count", 0) or r.get("private_segment_fixed_size", 0)}
     assert not bad, bad
     pers = {n: r for n, r in ks.items() if any(re.search(h, n) for h in KR.HOT_PERSISTENT)}      # round 6: the default GEMM of multi-round launches
-    assert len(pers) >= 6, sorted(pers)
+    assert len(pers) == 6, sorted(pers)
     bad = {n: (r.get("vgpr_spill_count", 0), r.get("private_segment_fixed_size", 0)) for n, r in pers.items() if r.get("vgpr_spill_count", 0) or r.get("private_segment_fixed_size", 0)}
     assert not bad, bad
     assert all(r.get("vgpr_count", 0) <= 512 for r in ks.values())

@@ -1,6 +1,6 @@
 """The persistent ring kernel (csrc/gemm_ring8p.h) against the one-tile-per-workgroup ring kernel on the step's multi-round GEMMs, ONE process:
 bit-equality of the outputs (same MFMA order, same epilogue arithmetic), then interleaved timing rounds on cold operands.
-usage: python tools/persist_ab.py [rounds]      (ullsam_set_gemm_tuning(2, 0 / 1) is the switch)"""
+usage: python tools/persist_ab.py [rounds]      (ullsam_set_gemm_tuning(2, 0 / 2) is the switch)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -11,7 +11,10 @@ from ullsam_amd.packing import pack_w13
 lib = _lib.load()
 dev = "cuda"
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-MODES = [int(m) for m in (sys.argv[2].split(",") if len(sys.argv) > 2 else ["0", "1"])]   # 0 one-tile kernel, 1 persistent, 3 persistent with request distance 3 (experiment)
+MODES = [int(m) for m in (sys.argv[2].split(",") if len(sys.argv) > 2 else ["0", "2"])]   # 0 one-tile kernel, 2 persistent (the library accepts no other value)
+for pz in MODES:
+    if lib.ullsam_set_gemm_tuning(2, pz) != 0:
+        raise SystemExit(lib.ullsam_last_error_string().decode())
 SHAPES = [  # name, M, N, K, act, bias, res
     ("llm.w13", 4324, 28672, 4096, 3, False, False), ("vit.qkv", 16384, 3840, 1280, 0, True, False), ("vit.lin1", 16384, 5120, 1280, 1, True, False),
     ("llm.wqkv.plain", 4324, 6144, 4096, 0, False, False), ("vit.lin1.plain", 16384, 5120, 1280, 0, False, False), ("llm.w13.plain", 4324, 28672, 4096, 0, False, False),
@@ -38,7 +41,7 @@ for name, M, N, K, act, hb, res in SHAPES:
             outs[pz] = ops.gemm(As[0], Ws[0], bias, act=act)
     torch.cuda.synchronize()
     ref = As[0].float() @ Ws[0].float().T
-    eq = {pz: (torch.equal(outs[0], outs[pz]), int((outs[0] != outs[pz]).sum().item())) for pz in MODES[1:]}   # (modes 5 - 7 are ablations: they differ by construction)
+    eq = {pz: (torch.equal(outs[0], outs[pz]), int((outs[0] != outs[pz]).sum().item())) for pz in MODES[1:]}
     Cs = [torch.zeros(M, n_out, device=dev, dtype=torch.float32 if res else torch.bfloat16) for _ in range(ncopy)]
     times = {pz: [] for pz in MODES}
     for r in range(rounds):

@@ -24,7 +24,7 @@ def main():
         times = {v: [] for v in variants}
         for r in range(rounds):
             for v in (variants if r % 2 == 0 else variants[::-1]):   # ABBA: the variant measured second in a round comes out ~0.5 % faster
-                head, _, pz = str(v).partition("p")     # "7p0" = dispatch mask 7 with the one-tile ring kernel (ullsam_set_gemm_tuning key 2: 0 one tile per workgroup, 2 persistent = the default, 1 / 4 the earlier persistent forms)
+                head, _, pz = str(v).partition("p")     # "7p0" = dispatch mask 7 with the one-tile ring kernel (ullsam_set_gemm_tuning key 2: 0 one tile per workgroup, 2 persistent = the default)
                 lib.ullsam_set_gemm_tuning(2, int(pz) if pz else 2)   # (2 = the library's default)
                 head, _, gm = head.partition("g")       # "7g8" = dispatch mask 7 with raster groups of 8 tile rows
                 lib.ullsam_set_gemm_tuning(0, int(gm) if gm else 4)

@@ -951,7 +951,7 @@ static int launch_win14(const AttnArgs& a, hipStream_t s) {
 //  kilo-cycles each, 9 of them arithmetic, the rest the one barrier per problem (14 waves in lockstep) and request issue against a saturated memory system (~500 cycles per
 //  1 KiB piece and wave); removed (git acf202b has it).
 // ------------------------------------------------------------------------------------------------------
-template <int ABL>   // ABL: 0 = the kernel; diagnostic builds (attention variants 20 .. 22): 1 = fetch + table phase only, 2 = no K / V fetch, 3 = no stores; 4 = s_memtime stamps (ullsam_set_attn_debug)
+template <bool STAMP>   // STAMP: the diagnostic build with s_memtime stamps (ullsam_set_attn_debug)
 __global__ __launch_bounds__(448, 4) void win14r_attn_kernel(AttnArgs p) {
     typedef bf16 T;
     constexpr int HD = 80, G = 14, NK = 196, NW = 7;
@@ -969,9 +969,9 @@ __global__ __launch_bounds__(448, 4) void win14r_attn_kernel(AttnArgs p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ql = lane & 15, g = lane >> 4;
     float* scr = reinterpret_cast<float*>(smem + 2 * OPB) + wave * (SCRB / 4);
-    // ABL == 4: s_memtime stamps of every wave (tools/probes/win_stamps.py): [workgroup][wave][8]
+    // STAMP: s_memtime stamps of every wave (tools/probes/win_stamps.py): [workgroup][wave][8]
     auto stamp = [&](const int i) __attribute__((always_inline)) {
-        if (ABL == 4) {
+        if (STAMP) {
             const unsigned long long t = __builtin_amdgcn_s_memtime();
             if (lane == 0) p.dbg[((size_t)blockIdx.x * NW + wave) * 8 + i] = t;
         }
@@ -1012,10 +1012,8 @@ __global__ __launch_bounds__(448, 4) void win14r_attn_kernel(AttnArgs p) {
                 ks = bk;
                 vs = bv;
             }
-            if (ABL != 2) {
-                __builtin_amdgcn_global_load_lds(GLB_PTR(ks + 8 * c), LDS_PTR(Ks + i * 1024), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds(GLB_PTR(vs + 8 * c), LDS_PTR(Vs + i * 1024), 16, 0, 0);
-            }
+            __builtin_amdgcn_global_load_lds(GLB_PTR(ks + 8 * c), LDS_PTR(Ks + i * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(GLB_PTR(vs + 8 * c), LDS_PTR(Vs + i * 1024), 16, 0, 0);
         }
     }
 
@@ -1197,62 +1195,50 @@ __global__ __launch_bounds__(448, 4) void win14r_attn_kernel(AttnArgs p) {
         __builtin_amdgcn_sched_barrier(0);
         // ---- normalise; lane (q, g) holds dims 16 d + 4 g .. + 3 of its query: 8-byte pieces.  Through the wave's scratch as a [16 queries][160 B] image and out as
         // 16-byte stores, ten consecutive lanes per token (the 8-byte scattered stores of the first version cost 24 us of an 86 us launch)
-        if (ABL != 3 || o[5][0] == 12345.f) {
-            const float inv_l = 1.0f / o[5][0];
-            char* ob = reinterpret_cast<char*>(scr);
+        const float inv_l = 1.0f / o[5][0];
+        char* ob = reinterpret_cast<char*>(scr);
 #pragma unroll
-            for (int d = 0; d < 5; ++d) {
-                bf16x4_t v;
-                v[0] = (bf16)(o[d][0] * inv_l); v[1] = (bf16)(o[d][1] * inv_l); v[2] = (bf16)(o[d][2] * inv_l); v[3] = (bf16)(o[d][3] * inv_l);
-                *reinterpret_cast<bf16x4_t*>(ob + ql * 160 + 32 * d + 8 * g) = v;
-            }
-            asm volatile("" ::: "memory");
-            T* orow = reinterpret_cast<T*>(p.out) + (long)b * p.o_bs + (long)head * p.o_hs;
-            const int qgy = wy * G + cur_qh;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const int c = lane + 64 * r;          // 16-byte chunk of the image: query c / 10, chunk c % 10
-                const int qq = c / 10, ch = c - 10 * qq;
-                const int gx = wx * G + qq;
-                if (c < 16 * 10 && qq < G && gx < p.grid_w) {
-                    const uint4 v = *reinterpret_cast<const uint4*>(ob + 16 * c);
-                    *reinterpret_cast<uint4*>(orow + ((long)qgy * p.grid_w + gx) * p.o_ts + 8 * ch) = v;
-                }
-            }
-            asm volatile("" ::: "memory");
+        for (int d = 0; d < 5; ++d) {
+            bf16x4_t v;
+            v[0] = (bf16)(o[d][0] * inv_l); v[1] = (bf16)(o[d][1] * inv_l); v[2] = (bf16)(o[d][2] * inv_l); v[3] = (bf16)(o[d][3] * inv_l);
+            *reinterpret_cast<bf16x4_t*>(ob + ql * 160 + 32 * d + 8 * g) = v;
         }
+        asm volatile("" ::: "memory");
+        T* orow = reinterpret_cast<T*>(p.out) + (long)b * p.o_bs + (long)head * p.o_hs;
+        const int qgy = wy * G + cur_qh;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int c = lane + 64 * r;          // 16-byte chunk of the image: query c / 10, chunk c % 10
+            const int qq = c / 10, ch = c - 10 * qq;
+            const int gx = wx * G + qq;
+            if (c < 16 * 10 && qq < G && gx < p.grid_w) {
+                const uint4 v = *reinterpret_cast<const uint4*>(ob + 16 * c);
+                *reinterpret_cast<uint4*>(orow + ((long)qgy * p.grid_w + gx) * p.o_ts + 8 * ch) = v;
+            }
+        }
+        asm volatile("" ::: "memory");
     };
     stamp(2);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     stamp(3);
     __syncthreads();                           // every wave's pieces have landed
     stamp(4);
-    if (ABL == 1) {
-        if ((live[0] || live[1]) && thr0[3] + thr1[3] + cinit1[0] == 12345.f && qv) reinterpret_cast<T*>(p.out)[0] = (T)cinit0[0];
-        return;
-    }
     if (live[0]) main_group(0, qf0, cinit0, thr0);
     stamp(5);
     if (live[1]) main_group(1, qf1, cinit1, thr1);
     stamp(6);
 }
 
-static int launch_win14r(const AttnArgs& a, hipStream_t s, int abl = 0) {
+static int launch_win14r(const AttnArgs& a, hipStream_t s) {
     constexpr int LDS = 2 * 31 * 1024 + 7 * 16 * 160;
     static PerDeviceOnce attr;
     if (attr.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(win14r_attn_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(win14r_attn_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(win14r_attn_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(win14r_attn_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(win14r_attn_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(win14r_attn_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(win14r_attn_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     }
     const dim3 grid(a.H * a.B * a.nwin), blk(448);
-    if (a.dbg) win14r_attn_kernel<4><<<grid, blk, LDS, s>>>(a);
-    else if (abl == 1) win14r_attn_kernel<1><<<grid, blk, LDS, s>>>(a);
-    else if (abl == 2) win14r_attn_kernel<2><<<grid, blk, LDS, s>>>(a);
-    else if (abl == 3) win14r_attn_kernel<3><<<grid, blk, LDS, s>>>(a);
-    else win14r_attn_kernel<0><<<grid, blk, LDS, s>>>(a);
+    if (a.dbg) win14r_attn_kernel<true><<<grid, blk, LDS, s>>>(a);
+    else win14r_attn_kernel<false><<<grid, blk, LDS, s>>>(a);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -1932,7 +1918,7 @@ extern "C" int ullsam_vit_attention(int dtype, const void* qkv, void* out, const
         if (dtype == 1 && window == 14 && hd == 80 && g_attn_variant != 1 && g_attn_variant != 2 && g_attn_variant != 13 && (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)qkv_bias | (uintptr_t)rel_h | (uintptr_t)rel_w) & 15) == 0) {   // (the kernel reads the rel-pos tables 16 bytes at a time too)
             a.q_pos0 = (g_attn_variant >= 3 && g_attn_variant <= 8) ? g_attn_variant - 3 : 0;
             a.dbg = g_attn_dbg;
-            return launch_win14r(a, s, (g_attn_variant >= 20 && g_attn_variant <= 22) ? g_attn_variant - 19 : 0);
+            return launch_win14r(a, s);
         }
         if (dtype == 1 && window == 14 && hd == 80 && g_attn_variant != 1 && g_attn_variant != 2) return launch_win14(a, s);
         // window = 196 queries: one 7-wave workgroup (128-key tiles) or two 4-wave workgroups (64-key tiles, 3 resident per CU)

@@ -18,6 +18,7 @@
 //                       from the accumulators (swapped operands, permuted weight rows, lane-pair swap).
 //   gemm_ring8p_kernel  (gemm_ring8p.h, round 6) the ring kernel as a persistent grid -- workgroups walk tiles with the LDS ring kept full across tile borders: launches of more
 //                       than one round of tiles with a direct epilogue (llm.w13, llm.wqkv + RoPE, vit.qkv, vit.lin1 of the bench step); outputs bit-equal to gemm_ring8_kernel.
+//                       ONE schedule (two barriers per stage, uniform trips, both groups' epilogues together), six shapes, each plain and stamped.
 //                       Split-K form (EMODE 2, launch_gemm_ring_splitk + splitk_finish_kernel): launches of <= 128 tiles under a long K (1081 x 4096 outputs: a batch-1
 //                       prefill, the frozen LLM of a training step) run up to 8 K ranges side by side into fp32 planes of the workspace, added in order.
 //   gemm256_kernel      256x256 tile, two 64 KiB stages, staggered two-group schedule (L0|C0|L1|C1), split-K tail + gemm256_tail_reduce_kernel,
@@ -28,7 +29,8 @@
 //   gemm256f8_kernel    the 256x256 two-buffer loop on v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3 ViT linears, BASELINE configs[4]).
 //   gemm_skinny_*       M <= 8 (decode step): weight-streaming, no tiles.
 // Variants that were built, measured and removed (a 256x128 three-stage ring, a persistent two-buffer kernel, a four-wave 512-register
-// kernel, a stream-K tail, the RoPE epilogue on the ring): DESIGN.md section 7 keeps their numbers.
+// kernel, a stream-K tail, the RoPE epilogue on the ring; the persistent ring's first and one-barrier schedules, its request distance of three
+// and its ablation builds): DESIGN.md section 7 keeps their numbers.
 // Epilogues: bias / GELU(erf) / ReLU / SwiGLU pair / fp32 residual (optionally row-broadcast, for pos_embed), fused.
 #include "common.h"
 #include <type_traits>
@@ -1274,7 +1276,7 @@ static int ring_splitk_plan(const GemmArgs& a, int* shape) {
 #include "gemm_ring8p.h"
 // Persistent form (gemm_ring8p.h) for launches of MORE than one round of tiles whose shape and epilogue it takes; everything else -- one-round
 // launches, ragged N, K not a multiple of 128, the LDS-staged epilogues -- stays on the one-tile-per-workgroup kernel.
-static int g_persist = 2;      // ullsam_set_gemm_tuning(2, v): 0 one tile per workgroup; 2 (default) persistent ring, uniform trips, both groups' epilogues together (-0.5 % of the bench step, outputs bit-equal); 1 / 4 / 5 - 7: the earlier persistent forms and the ablations
+static int g_persist = 2;      // ullsam_set_gemm_tuning(2, v): 0 one tile per workgroup; 2 (default) persistent ring, uniform trips, both groups' epilogues together (-0.5 % of the bench step, outputs bit-equal).  No other value: the earlier persistent forms and the ablations that 1 and 4 - 7 selected are gone
 static int cu_count() {
     static int n[32] = {};
     int d = 0;
@@ -1296,17 +1298,8 @@ static bool ring_persist_ok(const GemmArgs& a) {
 }
 template <int MI0, int MI1, int NTW, int EMODE = 0>
 static int launch_ring(const GemmArgs& a, hipStream_t stream) {
-    if (ring_persist_ok<16 * (MI0 + MI1), 64 * NTW, NTW, EMODE>(a)) {
-        if (g_persist == 2) return launch_gemm_ring8p<MI0, MI1, NTW, EMODE, 2, 2>(a, stream, cu_count());   // uniform trips, both groups' epilogues at the same time
-        if constexpr (EMODE == 0) { if (g_persist == 4) return launch_gemm_ring8p<MI0, MI1, NTW, EMODE, 2, 1>(a, stream, cu_count()); }   // one barrier per stage
-        if constexpr (EMODE == 0 && MI0 == 9) {   // ablations of the 272x256 loop (wrong results: timing only)
-            if (g_persist == 5) return launch_gemm_ring8p<MI0, MI1, NTW, EMODE, 2, 0, 1>(a, stream, cu_count());
-            if (g_persist == 6) return launch_gemm_ring8p<MI0, MI1, NTW, EMODE, 2, 0, 2>(a, stream, cu_count());
-            if (g_persist == 7) return launch_gemm_ring8p<MI0, MI1, NTW, EMODE, 2, 0, 3>(a, stream, cu_count());
-        }
-        return launch_gemm_ring8p<MI0, MI1, NTW, EMODE>(a, stream, cu_count());
-    }
-    return launch_gemm_ring8<MI0, MI1, NTW, EMODE>(a, stream);
+    return ring_persist_ok<16 * (MI0 + MI1), 64 * NTW, NTW, EMODE>(a) ? launch_gemm_ring8p<MI0, MI1, NTW, EMODE>(a, stream, cu_count())
+                                                                      : launch_gemm_ring8<MI0, MI1, NTW, EMODE>(a, stream);
 }
 static int launch_gemm_v6(const GemmArgs& a, hipStream_t stream) { return launch_ring<8, 8, 4>(a, stream); }   // 256 x 256
 static int launch_gemm_v8(const GemmArgs& a, hipStream_t stream) { return launch_ring<8, 8, 5>(a, stream); }   // 256 x 320
@@ -1477,7 +1470,7 @@ extern "C" int ullsam_gemm_fp8(const void* A8, long lda, const float* a_scale, c
 extern "C" int ullsam_set_gemm_tuning(int key, int value) {
     if (key == 0 && value >= 1 && value <= 1024) { g_group_m = value; return 0; }
     if (key == 1 && value >= 0 && value <= 7) { g_auto_mask = value; return 0; }
-    if (key == 2 && value >= 0 && value <= 7 && value != 3) { g_persist = value; return 0; }
+    if (key == 2 && (value == 0 || value == 2)) { g_persist = value; return 0; }
     if (key == 3 && value >= 0 && value <= 2) { g_ring_splitk = value; return 0; }
     ullsam_set_error("ullsam_set_gemm_tuning: unknown key %d / bad value %d", key, value);
     return -1;

@@ -4,15 +4,17 @@
 //   * a grid of at most one workgroup per CU; workgroup b walks the tiles b, b + G, b + 2 G, ... (G = gridDim.x) in the dispatch order the
 //     one-tile-per-workgroup kernel has, so the sets of tiles that run together (and share an XCD's L2) are the same;
 //   * the LDS ring NEVER drains at a tile border: the last two load slots of a tile request stages 0 and 1 of the NEXT tile (in the one-tile kernel they request
-//     nothing); in the DEFAULT schedule (SCHED 2) that is all -- every trip of the K loop is the same code, the next tile's first load slot requests its stage 2 as
-//     every load slot requests the stage two ahead; the first schedule (SCHED 0) also requested stage 2 at the border and had a request-free first stage, which cost it
-//     peeled first / last trips;
+//     nothing), and that is all -- the border requests nothing, the next tile's first load slot requests its stage 2 (behind the border's vmcnt(0)) as every load slot
+//     requests the stage two ahead, so the K loop is ONE loop of identical trips, the last trip's stages 2 / 3 taking the next tile's scalar offsets through two selects
+//     per TRIP (a request at the border and a request-free first stage cost the first schedule peeled first / last trips, where the 256x320 instantiation spilled: DESIGN section 7);
 //   * loads and stores share `vmcnt` on gfx950 and complete in issue order, which is what sank the persistent kernels of rounds 2 and 3 (the next tile's counted
 //     waits sat behind the previous tile's 16 - 40 store acknowledgements).  Here the border ends with ONE `s_waitcnt vmcnt(0)` -- stages 0' and 1' have long landed,
 //     only the youngest stores are still on their way (330 - 670 cycles by the stamps) -- and no counted wait of the next tile has a store in front of it;
-//   * the two wave groups keep their one-slot stagger inside a tile; at the border (SCHED 2) group 0 waits one extra barrier for group 1's last matrix slot, both
-//     groups convert and store their accumulators AT THE SAME TIME (as in the one-tile kernel), and group 1 takes one extra barrier behind its vmcnt(0) to fall one
-//     slot behind again (SCHED 0 ran the two epilogues one after the other and so gave back the prologue it saved);
+//   * inside a tile the stage is the one-tile kernel's: two barriers, the two wave groups' load and matrix slots strictly alternating one slot apart (a load slot's own work ends
+//     ~340 cycles into a slot of ~680 whose length is the partner's 512 - 576 matrix cycles plus ~120 cycles around the two barriers); at the border group 0 waits one extra barrier
+//     for group 1's last matrix slot, both groups convert and store their accumulators AT THE SAME TIME (as in the one-tile kernel), and group 1 takes one extra barrier behind its
+//     vmcnt(0) (for group 0's first load slot) to fall one slot behind again (the two epilogues one after the other gave back the prologue the kernel saves; one barrier per stage
+//     and requests three stages ahead were measured too: DESIGN section 7);
 //   * requests go through BUFFER descriptors (`buffer_load_dwordx4 ... offen lds`: descriptor + per-lane offset + scalar offset): the per-lane
 //     offsets are the same in every tile, a tile switch is one scalar per operand, and rows past M are out of the descriptor's range (no fetch, no
 //     clamp) -- so ONE copy of the load slot serves every stage of every tile, with the request's scalar offset switched two stages before a border;
@@ -50,20 +52,8 @@ __device__ __forceinline__ void blds16_imm(u32x4 desc, unsigned int voff, unsign
                  :: "v"(voff), "s"(desc), "s"(soff), "s"(wave_lds_base), "n"(MOFF) : "memory", "m0");
 }
 template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N <= 12, "counted waits of the ring");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-    else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else if constexpr (N == 11) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+    static_assert(N >= 0 && N <= 6, "counted waits of the ring: one stage of a wave's pieces (at most three per operand) in flight");
+    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
 }
 #pragma clang diagnostic pop
 // The lane id, re-derived from the hardware (two VALU instructions) at every use site of the persistent kernel's tile loop: a lane id kept in a register
@@ -84,21 +74,8 @@ __device__ __forceinline__ u32x4 raw_desc(const void* base, unsigned int bytes) 
     return d;
 }
 
-// DIST: stages between a request and its use in the two-barrier schedule (2: the one-tile kernel's; 3: an experiment).
-// SCHED 0: the one-tile kernel's schedule -- two barriers per stage, the groups' load and matrix slots strictly alternating.
-// SCHED 2: SCHED 0's stage (two barriers), but (a) every stage of every trip requests (the border requests nothing: the next tile's first load slot requests its stage 2 behind the border's
-//   vmcnt(0)), so the K loop is ONE loop of identical trips -- the last trip's stages 2 / 3 take the next tile's scalar offsets through two selects per TRIP -- with no peeled copies (the peeled
-//   first / last trips of SCHED 0 are where the 256x320 instantiation spilled); (b) the two wave groups run their epilogues AT THE SAME TIME, as in the one-tile kernel: group 0 waits one
-//   barrier at the border's start (for group 1's last matrix slot), group 1 one at its end (for group 0's first load slot) -- SCHED 0 ran them one after the other and gave back the prologue it saved.
-// SCHED 1: ONE barrier per stage.  Between two barriers group 0 runs [matrix slot of stage s, load slot of stage s + 1] and group 1 [load slot of stage s, matrix slot
-//   of stage s, counted wait]: the matrix pipe always has one group's instructions to run and a barrier's latency is paid once per stage, not twice (in-stage
-//   stamps of SCHED 0: a load slot's own work ends ~340 cycles into a slot of ~680 whose length is the partner's 512 - 576 matrix cycles plus ~120 cycles around the
-//   two barriers).  Safety with the four-slot ring: a stage is read by group 0 in the interval BEFORE the barrier after which group 1 reads it, so group 1's pieces
-//   must have landed one barrier earlier than in SCHED 0 -- group 1 requests THREE stages ahead (its slot was last read, by itself, two intervals earlier, and by
-//   group 0 three), group 0 two; every wave's counted wait still leaves exactly one stage of its own pieces in flight.
-// ABL (diagnostic, wrong results): 1 = the K loop issues no LDS-DMA request, 2 = no fragment read (the MFMAs run on whatever the registers hold), 3 = neither -- what a
-// stage costs without each ingredient (tools/persist_ab.py modes 5 / 6 / 7).
-template <int MI0, int MI1, int NTW, int EMODE = 0, bool STAMP = false, int DIST = 2, int SCHED = 0, int ABL = 0>
+// STAMP: the diagnostic build with the tile-level shader-clock stamps (ullsam_set_gemm_variant bits 15 + 16, tools/probes/ring8p_stamps.py).
+template <int MI0, int MI1, int NTW, int EMODE = 0, bool STAMP = false>
 __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef bf16 T;
@@ -165,7 +142,7 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
             glds16_sbase(reinterpret_cast<const char*>(p.bias), (unsigned int)c * 4u, (unsigned int)(uintptr_t)LDS_PTR(smem + BIAS_LDS + buf * 2048 + wave * 1024));
         }
     };
-    auto request_stage = [&](unsigned int ra, unsigned int rb, int slot) __attribute__((always_inline)) {   // all of this wave's pieces of one stage (prologue, tile border)
+    auto request_stage = [&](unsigned int ra, unsigned int rb, int slot) __attribute__((always_inline)) {   // all of this wave's pieces of one stage (the first tile's prologue)
         char* base = smem + slot * STG;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -177,22 +154,20 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
         if (STAMP && p.dbg && (tid & 255) == 0 && tile_k < 8) p.dbg[(((size_t)blockIdx.x * 2 + grp) * 8 + tile_k) * 4 + kk] = __builtin_amdgcn_s_memtime();
     };
 
-    // ---- first tile: bias row and stages 0, 1, 2 requested and landed (every tile then starts from the same state: stage 0 requests nothing)
+    // ---- first tile: bias row and stages 0, 1 requested and landed (every tile then starts from the same state: its first load slot requests its stage 2)
     int tm0, tn0;
     tile_of(blockIdx.x, tm0, tn0);
     bias_dma(tn0 * BN, 0);
     request_stage(tm0 * a_tile, tn0 * b_tile, 0);
     request_stage(tm0 * a_tile + 64, tn0 * b_tile + 64, 1);
-    if (SCHED == 0 || (SCHED == 1 && grp == 1)) request_stage(tm0 * a_tile + 128, tn0 * b_tile + 128, 2);
-    if constexpr (SCHED == 0 && DIST >= 3) request_stage(tm0 * a_tile + 192, tn0 * b_tile + 192, 3);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (grp == 1) __builtin_amdgcn_s_barrier();
 
     // ---- everything from here on per wave ROW (MIW sub-tile rows: compile-time) -- the tile loop, its K loop, the epilogue
-    auto core = [&](auto MIW_c, auto ROWW_c, auto GRP_c) __attribute__((always_inline)) {
-        constexpr int MIW = decltype(MIW_c)::value, GRP = decltype(GRP_c)::value;   // GRP: the wave group (SCHED 1 only; -1: both groups run this instantiation)
-        constexpr int DG = SCHED == 1 ? (GRP == 0 ? 2 : 3) : (SCHED == 2 ? 2 : DIST);                  // request distance of this group
+    auto core = [&](auto MIW_c, auto ROWW_c) __attribute__((always_inline)) {
+        constexpr int MIW = decltype(MIW_c)::value;
+        constexpr int DG = 2;   // request distance: stages between a request and its use (the one-tile kernel's)
         const int row_w = decltype(ROWW_c)::value >= 0 ? decltype(ROWW_c)::value : wm * (MI0 * 16);   // first tile row of this wave's row (run time when both rows share one instantiation)
         f32x4 acc[MIW][NTW];
 #pragma unroll
@@ -209,24 +184,17 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
             rd_a = (unsigned int)(uintptr_t)LDS_PTR(smem) + (unsigned int)row_w * 64u + lane_part;
             rd_b = (unsigned int)(uintptr_t)LDS_PTR(smem) + (unsigned int)(ASZ + wn * (16 * NTW) * 64) + lane_part;
         };
-        // (diagnostic build) shader-clock stamps INSIDE one stage (tile 1, trip 4, stage 1 of the trip) of every wave: [0] slot start, [1] requests and reads issued,
-        // [2] counted wait passed, [3] first barrier passed, [4] matrix instructions issued, [5] second barrier passed -> p.dbg[2^19 + (workgroup x 8 + wave) x 8 + k]
-        bool stamp_on = false;
-        unsigned long long ts[6] = {0, 0, 0, 0, 0, 0};
         // One stage: load slot (this wave's requests for the stage two ahead, alternated with the fragment reads of the current stage, then the counted
         // wait), barrier, matrix slot, barrier.  The K loop is unrolled by the ring's four slots, so that the slot of a stage (read slot J, request slot
         // (J + 2) & 3) and with it every LDS address -- the M0 value of a request, the offsets of the reads -- is a compile-time constant: a request is
         // THREE instructions (s_add_i32 m0, base, imm / s_nop / buffer_load ... offset:imm lds) where the one-tile kernel spends six plus the slot arithmetic
         // (its load slot is the critical path of a stage and carries ~35 scalar instructions per stage; here ~10).  The k offset of a request rides in the
         // instruction's immediate (64 bytes per stage, relative to the trip's scalar offset), so the scalar offsets move once per trip.
-        // KIND 0: requests nothing (stage 0 of a tile: its stage 2 went out at the border), 1: requests at so_a / so_b + 64 (J + 2) (this tile),
-        // 2: requests at so_a / so_b + 64 (J - 2) (stages 0 / 1 of the NEXT tile: so_* are its offsets).
-        auto stage = [&](auto J_c, auto KIND_c, unsigned int so_a, unsigned int so_b, auto NA_c, auto NB_c) __attribute__((always_inline)) {
-            constexpr int J = decltype(J_c)::value, KIND = decltype(KIND_c)::value;
+        // Every stage requests, at so_a / so_b + 64 (J + 2).
+        auto stage = [&](auto J_c, unsigned int so_a, unsigned int so_b, auto NA_c, auto NB_c) __attribute__((always_inline)) {
+            constexpr int J = decltype(J_c)::value;
             constexpr int NA = decltype(NA_c)::value, NB = decltype(NB_c)::value;
-            constexpr int RS = (J + DG) & 3, KOFF = KIND == 2 ? 64 * (J - (4 - DG)) : 64 * (J + DG);
-            static_assert(KIND != 2 || J >= 4 - DG, "only the last DG stages of a tile request the next tile");
-            static_assert(SCHED == 0 || KIND != 0, "SCHED 1 / 2: every stage requests");
+            constexpr int RS = (J + DG) & 3, KOFF = 64 * (J + DG);
             const unsigned int rq_a = so_a + KOFF, rq_b = so_b + KOFF;   // (two scalar adds per stage)
             // this stage's read bases: the wave's per-lane bases (rd_a / rd_b, below) + the slot's offset, ONE add each, pinned here -- left to itself
             // hipcc keeps a base register per slot and (where it cannot see that the swizzle depends on the lane only) per fragment: 20 registers and
@@ -242,26 +210,18 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
                 return f;
             };
             Frag<T> a8[MIW], b[NTW];
-            auto tstamp = [&](int k) __attribute__((always_inline)) {
-                if constexpr (STAMP && SCHED != 2 && J == 1 && KIND == 1) { if (stamp_on) ts[k] = __builtin_amdgcn_s_memtime(); }
-            };
-            tstamp(0);
             {
                 auto request = [&](auto QI_c) __attribute__((always_inline)) {   // request QI of this wave: A0 B0 A1 B1 A2 B2
                     constexpr int qi = decltype(QI_c)::value, i = qi >> 1;
-                    if constexpr (!(ABL & 1) && KIND != 0 && !(qi & 1) && i < NA) blds16_imm<RS * STG + i * 8192>(a_desc, a_off[i], rq_a, wbase);
-                    if constexpr (!(ABL & 1) && KIND != 0 && (qi & 1) && i < NB) blds16_imm<RS * STG + ASZ + i * 8192>(b_desc, b_off[i], rq_b, wbase);
+                    if constexpr (!(qi & 1) && i < NA) blds16_imm<RS * STG + i * 8192>(a_desc, a_off[i], rq_a, wbase);
+                    if constexpr ((qi & 1) && i < NB) blds16_imm<RS * STG + ASZ + i * 8192>(b_desc, b_off[i], rq_b, wbase);
                     __builtin_amdgcn_sched_barrier(0);
                 };
                 auto rd = [&](auto R_c) __attribute__((always_inline)) {
                     constexpr int r = decltype(R_c)::value;
                     if constexpr (r < NTW + MIW) {
-                        if constexpr (ABL & 2) {   // no read: an opaque "definition" so that the MFMAs keep their operands
-                            if constexpr (r < NTW) asm volatile("" : "=v"(b[r].v)); else asm volatile("" : "=v"(a8[r - NTW].v));
-                        } else {
-                            if constexpr (r < NTW) b[r] = frag_at(t_b + r * 1024);
-                            else a8[r - NTW] = frag_at(t_a + (r - NTW) * 1024);
-                        }
+                        if constexpr (r < NTW) b[r] = frag_at(t_b + r * 1024);
+                        else a8[r - NTW] = frag_at(t_a + (r - NTW) * 1024);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 };
@@ -278,99 +238,31 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
                 rd(std::integral_constant<int, 12>{}); rd(std::integral_constant<int, 13>{});
                 request(std::integral_constant<int, 5>{});
             }
-            tstamp(1);
-            auto counted_wait = [&]() __attribute__((always_inline)) {
-                if constexpr (KIND == 0) { /* nothing of this wave is in flight (the border's vmcnt(0)) */ }
-                else if constexpr (ABL & 1) { /* nothing was requested */ }
-                else if constexpr (SCHED == 1 || SCHED == 2) wait_vmcnt<NA + NB>();
-                else wait_vmcnt<(DIST - 1) * (NA + NB)>();   // the stage read NEXT has landed: only the youngest stages' pieces may be in flight
-            };
-            auto matrix_slot = [&]() __attribute__((always_inline)) {
-                __builtin_amdgcn_s_setprio(1);
+            wait_vmcnt<NA + NB>();   // the counted wait: the stage read NEXT has landed, only the youngest stage's pieces may be in flight
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_setprio(1);   // the matrix slot
 #pragma unroll
-                for (int i = 0; i < MIW; ++i)
+            for (int i = 0; i < MIW; ++i)
 #pragma unroll
-                    for (int j = 0; j < NTW; ++j) mma16(b[j], a8[i], acc[i][j]);
-                __builtin_amdgcn_s_setprio(0);
-            };
-            if constexpr (SCHED == 0 || SCHED == 2) {
-                counted_wait();
-                tstamp(2);
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                tstamp(3);
-                matrix_slot();
-                tstamp(4);
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                tstamp(5);
-            } else if constexpr (GRP == 0) {   // load slot, barrier, matrix slot (the next stage's load slot follows without a barrier)
-                counted_wait();
-                tstamp(2);
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                tstamp(3);
-                matrix_slot();
-                tstamp(4);
-                __builtin_amdgcn_sched_barrier(0);
-            } else {                           // load slot, matrix slot, counted wait, barrier
-                __builtin_amdgcn_sched_barrier(0);
-                tstamp(2);
-                matrix_slot();
-                tstamp(3);
-                __builtin_amdgcn_sched_barrier(0);
-                counted_wait();
-                tstamp(4);
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                tstamp(5);
-            }
-            if constexpr (STAMP && SCHED != 2 && J == 1 && KIND == 1) {
-                if (stamp_on && (threadIdx.x & 63) == 0) {
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) p.dbg[(1 << 19) + ((size_t)blockIdx.x * 8 + wave) * 8 + k] = ts[k];
-                }
-            }
+                for (int j = 0; j < NTW; ++j) mma16(b[j], a8[i], acc[i][j]);
+            __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
         };
         // the stages of one tile, four per trip.  sa / sb: scalar offsets of this tile's stage 0; san / sbn: of the next tile's (the last two load slots request its stages 0 / 1)
-        int tile_kk = 0;
         auto run_tile = [&](auto NA_c, auto NB_c, unsigned int sa, unsigned int sb, unsigned int san, unsigned int sbn) __attribute__((always_inline)) {
             using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
-            if constexpr (SCHED == 2) {
-                const int ntrip = st1 >> 2;
-                unsigned int ra = sa, rb = sb;
-                for (int t = 0; t < ntrip; ++t) {
-                    const bool last = t == ntrip - 1;   // (no in-stage stamps in this schedule: inside the one loop body they cost the loop its shape -- 3 x the cycles per stage; the tile-level stamps stay)
-                    const unsigned int ha = last ? san - 256u : ra, hb = last ? sbn - 256u : rb;   // stages 2 / 3 of the last trip request stages 0 / 1 of the next tile: (san - 256) + 64 (J + 2)
-                    stage(I0{}, I1{}, ra, rb, NA_c, NB_c);
-                    stage(I1{}, I1{}, ra, rb, NA_c, NB_c);
-                    stage(I2{}, I1{}, ha, hb, NA_c, NB_c);
-                    stage(I3{}, I1{}, ha, hb, NA_c, NB_c);
-                    ra += 256; rb += 256;
-                }
-            } else {
-            using K0 = std::integral_constant<int, SCHED == 1 ? 1 : 0>;        // stage 0 of a tile: SCHED 0 requests nothing there (its stage DIST went out at the border)
-            using KL0 = std::integral_constant<int, DG >= 4 ? 2 : 1>;
-            using KL1 = std::integral_constant<int, DG >= 3 ? 2 : 1>;          // the kinds of the last trip's stages: stage J requests the next tile when J + DG >= 4
-            using KL2 = std::integral_constant<int, DG >= 2 ? 2 : 1>;
-            stage(I0{}, K0{}, sa, sb, NA_c, NB_c);
-            stage(I1{}, I1{}, sa, sb, NA_c, NB_c);
-            stage(I2{}, I1{}, sa, sb, NA_c, NB_c);
-            stage(I3{}, I1{}, sa, sb, NA_c, NB_c);
-            unsigned int ra = sa + 256, rb = sb + 256;
-            for (int t = 2; t < (st1 >> 2); ++t) {
-                if constexpr (STAMP) stamp_on = p.dbg && tile_kk == 1 && t == 4;
-                stage(I0{}, I1{}, ra, rb, NA_c, NB_c);
-                stage(I1{}, I1{}, ra, rb, NA_c, NB_c);
-                stage(I2{}, I1{}, ra, rb, NA_c, NB_c);
-                stage(I3{}, I1{}, ra, rb, NA_c, NB_c);
+            const int ntrip = st1 >> 2;
+            unsigned int ra = sa, rb = sb;
+            for (int t = 0; t < ntrip; ++t) {
+                const bool last = t == ntrip - 1;   // (no stamps inside a stage: inside the one loop body they cost the loop its shape -- 3 x the cycles per stage; the tile-level stamps stay)
+                const unsigned int ha = last ? san - 256u : ra, hb = last ? sbn - 256u : rb;   // stages 2 / 3 of the last trip request stages 0 / 1 of the next tile: (san - 256) + 64 (J + 2)
+                stage(I0{}, ra, rb, NA_c, NB_c);
+                stage(I1{}, ra, rb, NA_c, NB_c);
+                stage(I2{}, ha, hb, NA_c, NB_c);
+                stage(I3{}, ha, hb, NA_c, NB_c);
                 ra += 256; rb += 256;
-            }
-            if constexpr (STAMP) stamp_on = false;
-            stage(I0{}, KL0{}, ra, rb, NA_c, NB_c);
-            if constexpr (KL1::value == 2) stage(I1{}, KL1{}, san, sbn, NA_c, NB_c); else stage(I1{}, KL1{}, ra, rb, NA_c, NB_c);
-            if constexpr (KL2::value == 2) stage(I2{}, KL2{}, san, sbn, NA_c, NB_c); else stage(I2{}, KL2{}, ra, rb, NA_c, NB_c);
-            stage(I3{}, I2{}, san, sbn, NA_c, NB_c);
             }
         };
 
@@ -394,14 +286,13 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
                 }
             }
             stamp(tile_k, 1);
-            // ---- tile border.  Stage DIST of the next tile goes out before anything else (DIST 2: ring slot 2 was last read two stages ago by both groups).
-            // SCHED 2: group 0, one slot ahead, takes ONE extra barrier inside its epilogue (it pairs with the barrier that ends group 1's last matrix slot), so that group 1's epilogue starts
+            // ---- tile border.  Nothing is requested here: the next tile's first load slot requests as every other one; it starts behind this border's vmcnt(0).
+            // Group 0, one slot ahead, takes ONE extra barrier inside its epilogue (it pairs with the barrier that ends group 1's last matrix slot), so that group 1's epilogue starts
             // beside group 0's instead of behind it; placed after the first sub-tile row's conversions and stores (border_sync(1) at the top of the loops' second trip), not at the
             // border's start: group 0 then works through group 1's last matrix slot instead of idling at the barrier for it.  Exactly one call with i == 1 (i == 2 in the two-row loop) per epilogue path.
             auto border_sync = [&](int i, int at) __attribute__((always_inline)) {
-                if constexpr (SCHED == 2) { if (i == at && grp == 0) { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); } }
+                if (i == at && grp == 0) { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); }
             };
-            if constexpr (SCHED == 0) request_stage(san + 64 * DIST, sbn + 64 * DIST, DIST);   // (SCHED 1: the next tile's first load slot requests as every other one; it starts behind this border's vmcnt(0))
             const int m0 = tm * BM, n0 = tn * BN;
             // The epilogue's per-lane quantities come from an OPAQUE copy of the lane id made in every trip (see the compiler notes above).
             const int lane_e = fresh_lane();
@@ -610,53 +501,46 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
             }
             stamp(tile_k, 2);
             if (has_next) bias_dma(tnn * BN, par ^ 1);
-            // stages 1' and 2' landed, this tile's stores acknowledged: nothing of this tile sits in front of the next one's counted waits (and no
+            // the next tile's stages 0 and 1 landed, this tile's stores acknowledged: nothing of this tile sits in front of the next one's counted waits (and no
             // LDS-DMA is in flight when the last tile's waves end)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_waitcnt(0x0F70);   // the same wait where hipcc's wait-count pass can see it: otherwise it protects the epilogue's loads / stores with waits of its own INSIDE the K loop
             stamp(tile_k, 3);
-            if constexpr (SCHED == 2) { if (grp == 1) __builtin_amdgcn_s_barrier(); }   // ... and group 1 falls back one slot behind group 0 (pairs with the barrier that ends group 0's next load slot, or the kernel's last one)
+            if (grp == 1) __builtin_amdgcn_s_barrier();   // ... and group 1 falls back one slot behind group 0 (pairs with the barrier that ends group 0's next load slot, or the kernel's last one)
             if (!has_next) break;
 #pragma unroll
             for (int i = 0; i < MIW; ++i)
 #pragma unroll
                 for (int j = 0; j < NTW; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
             v = vn; tm = tmn; tn = tnn;
-            par ^= 1; ++tile_k; tile_kk = tile_k;
+            par ^= 1; ++tile_k;
         }
     };
-    if constexpr ((SCHED == 0 || SCHED == 2) && MI0 == MI1) core(std::integral_constant<int, MI0>{}, std::integral_constant<int, -1>{}, std::integral_constant<int, -1>{});
+    if constexpr (MI0 == MI1) core(std::integral_constant<int, MI0>{}, std::integral_constant<int, -1>{});
     else {
-        if (wm == 0) core(std::integral_constant<int, MI0>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-        else core(std::integral_constant<int, MI1>{}, std::integral_constant<int, MI0 * 16>{}, std::integral_constant<int, 1>{});
+        if (wm == 0) core(std::integral_constant<int, MI0>{}, std::integral_constant<int, 0>{});
+        else core(std::integral_constant<int, MI1>{}, std::integral_constant<int, MI0 * 16>{});
     }
     if (grp == 0) __builtin_amdgcn_s_barrier();
 }
 
-template <int MI0, int MI1, int NTW, int EMODE = 0, int DIST = 2, int SCHED = 0, int ABL = 0>
+template <int MI0, int MI1, int NTW, int EMODE = 0>
 static int launch_gemm_ring8p(GemmArgs a, hipStream_t stream, int max_wgs) {
     constexpr int BM = 16 * (MI0 + MI1), BN = 64 * NTW;
     constexpr int LDS = 4 * (BM + BN) * 64 + 4096;   // the ring + two bias rows
     static_assert(LDS <= 163840, "160 KiB of LDS per CU");
-    constexpr bool HAS_STAMP = DIST == 2 && ABL == 0;
     static PerDeviceOnce attr_set;
     if (attr_set.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring8p_kernel<MI0, MI1, NTW, EMODE, false, DIST, SCHED, ABL>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if constexpr (HAS_STAMP) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring8p_kernel<MI0, MI1, NTW, EMODE, true, DIST, SCHED, ABL>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring8p_kernel<MI0, MI1, NTW, EMODE, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring8p_kernel<MI0, MI1, NTW, EMODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     }
     a.tiles_m = (a.M + BM - 1) / BM;
     a.tiles_n = a.N / BN;
     a.full_tiles = a.tiles_m * a.tiles_n;
     a.ksplit = 1;
     const int grid = a.full_tiles < max_wgs ? a.full_tiles : max_wgs;
-    if constexpr (HAS_STAMP) {
-        if (a.dbg) {
-            gemm_ring8p_kernel<MI0, MI1, NTW, EMODE, true, DIST, SCHED, ABL><<<dim3(grid), dim3(512), LDS, stream>>>(a);
-            ULLSAM_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    gemm_ring8p_kernel<MI0, MI1, NTW, EMODE, false, DIST, SCHED, ABL><<<dim3(grid), dim3(512), LDS, stream>>>(a);
+    if (a.dbg) gemm_ring8p_kernel<MI0, MI1, NTW, EMODE, true><<<dim3(grid), dim3(512), LDS, stream>>>(a);
+    else gemm_ring8p_kernel<MI0, MI1, NTW, EMODE, false><<<dim3(grid), dim3(512), LDS, stream>>>(a);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
