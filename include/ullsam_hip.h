@@ -420,6 +420,38 @@ int ullsam_mosaic_compact(const int* areas_raw, const int* boxes_raw, const int*
                           int* areas, int* boxes, int* K, void* stream);
 int ullsam_mosaic_paste(const int* tiles, int T, int th, int tw, const int* base, long G, const int* cores, int max_rows,
                         const int* label_of_global, int H, int W, int* labels, void* stream);
+/* Z-stacks and time-lapse: per-plane label maps linked along the third axis into 3-D objects (csrc/stack.hip; integer work, bit-exact with the
+   host form utils.stack.link_label_stack; definition in DESIGN.md "7b, continued (stacks)").  planes i32 [Z, H, W], plane z with ids 0..K_z;
+   base i32 [Z + 1] = the exclusive sum of the K_z, G = base[Z] <= 2^31 - 2; the global id of (z, l > 0) is base[z] + l.  Z <= 65535,
+   H, W <= 46340.  0 < num <= den < 2^31.  flags i32 [4]: [0] = 1 when an id lies outside 0..K_z (it reads as background) or a table holds
+   what no stack produces (it is skipped), [1] = 1 when the pair table refused a key, [2] = the number of distinct pairs; ([3] is free for K).
+   stack_pairs: zeroes its outputs, then counts areas i32 [G + 1] = the pixels of g in its own plane, and the pairs of every two consecutive
+     planes: keys u64 [cap] (g_a << 32 | g_b, a in plane z, b in plane z + 1, both > 0; 0 = empty slot, open addressing), counts i32 [cap] =
+     #{p : plane_z(p) = a, plane_z+1(p) = b}.  cap a power of two >= 2 * max_pairs; more than max_pairs distinct pairs set flags[1] / show
+     in flags[2].
+   stack_best: a slot is a candidate when n > 0 and n * den >= num * u, u = A(a) + A(b) - n.  succ i32 [G + 1][a] = the partner b of a's best
+     candidate, pred i32 [G + 1][b] = the partner a of b's best candidate, 0 where there is none; best = the largest n / u, compared exactly
+     (n1 * u2 against n2 * u1 in 64 bits), equal ones by the smaller partner id.  cap is any length; a key needs 1 <= g_a < g_b <= G.
+   stack_link: parent i32 [G + 1] = the smallest global id of the component of g.  With succ / pred (stack_best's): (a, b) is linked iff
+     succ[a] = b and pred[b] = a, components are chains (keys, counts, areas are not read).  With succ = pred = NULL: every candidate of
+     the table is a link.
+   stack_stats: voxels_raw i64 [G + 1], zrange_raw i32 [G + 1, 2] (first and last plane), boxes_raw i32 [G + 1, 4] (inclusive XYXY over all
+     planes) per REPRESENTATIVE; others keep 0 voxels, the range INT_MAX, -1 and the box INT_MAX, INT_MAX, -1, -1.
+   stack_compact: a representative is dropped when its voxels are 0 or < min_volume or it spans fewer than min_planes planes, the others
+     are renumbered 1..K by ascending id: label_of_global i32 [G + 1] (0 = dropped, members follow their representative), voxels i64 [G] /
+     zrange i32 [G, 2] / boxes i32 [G, 4] (first K entries), K i32 [1].
+   stack_relabel: volume i32 [Z, H, W][z, p] = label_of_global[base[z] + plane_z[p]] (0 where the plane says 0); indexed in 64 bits. */
+int ullsam_stack_pairs(const int* planes, int Z, int H, int W, const int* base, long G, unsigned long long* keys, int* counts, long cap,
+                       int max_pairs, int* areas, int* flags, void* stream);
+int ullsam_stack_best(const unsigned long long* keys, const int* counts, long cap, const int* areas, long G, long num, long den, int* succ,
+                      int* pred, int* flags, void* stream);
+int ullsam_stack_link(const int* succ, const int* pred, const unsigned long long* keys, const int* counts, long cap, const int* areas, long G,
+                      long num, long den, int* parent, int* flags, void* stream);
+int ullsam_stack_stats(const int* planes, int Z, int H, int W, const int* base, long G, const int* parent, long* voxels_raw, int* zrange_raw,
+                       int* boxes_raw, int* flags, void* stream);
+int ullsam_stack_compact(const long* voxels_raw, const int* zrange_raw, const int* boxes_raw, const int* parent, long G, int min_planes,
+                         long min_volume, int* label_of_global, long* voxels, int* zrange, int* boxes, int* K, void* stream);
+int ullsam_stack_relabel(const int* planes, int Z, int H, int W, const int* base, long G, const int* label_of_global, int* volume, void* stream);
 /* Per-instance measurements and contacts from a label image (csrc/measure.hip; integer work, bit-exact with the host forms
    utils.measure.measure_instances / label_contacts; definition in DESIGN.md "7b, continued: measurements").  labels i32 [H, W] with ids
    0..K, 0 = background, 1 <= H, W <= 46340 (x * x and every area stay below 2^31, every sum below 2^62), K <= 2^31 - 2.  Row k - 1 of every

@@ -103,6 +103,12 @@ SIGNATURES = {
     "ullsam_mosaic_stats": [vp, i32, i32, i32, vp, i64, vp, i32, vp, i32, i32, vp, vp, vp, vp],
     "ullsam_mosaic_compact": [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp],
     "ullsam_mosaic_paste": [vp, i32, i32, i32, vp, i64, vp, i32, vp, i32, i32, vp, vp],
+    "ullsam_stack_pairs": [vp, i32, i32, i32, vp, i64, vp, vp, i64, i32, vp, vp, vp],
+    "ullsam_stack_best": [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp],
+    "ullsam_stack_link": [vp, vp, vp, vp, i64, vp, i64, i64, i64, vp, vp, vp],
+    "ullsam_stack_stats": [vp, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp],
+    "ullsam_stack_compact": [vp, vp, vp, vp, i64, i32, i64, vp, vp, vp, vp, vp, vp],
+    "ullsam_stack_relabel": [vp, i32, i32, i32, vp, i64, vp, vp, vp],
     "ullsam_measure_instances": [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "ullsam_label_contacts": [vp, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp],
     "ullsam_label_d1": [vp, i32, i32, i32, vp, vp, vp, vp],

@@ -488,3 +488,47 @@ class SamAutomaticMaskGenerator:
             from .utils import measure as MS
             return labels, out, MS.measure_instances(labels, torch.from_numpy(np.ascontiguousarray(image)), num=len(areas), device=dev)
         return labels, out
+
+    @torch.no_grad()
+    def generate_stack_label_volume(self, images, order: str = "area", min_visible_area: int = 0, iou=(1, 4), mode: str = "mutual",
+                                    min_planes: int = 1, min_volume: int = 0):
+        """Segment everything on every plane of a z-stack or every frame of a time-lapse, then link the per-plane instances along the third axis
+        into 3-D objects: every plane goes through generate_label_map(plane, order=order, min_visible_area=min_visible_area), its label map stays
+        on the device, and utils.stack.link_label_stack (csrc/stack.hip) links two labels of consecutive planes when their IoU is at least
+        iou = (num, den) and -- mode="mutual" -- each is the other's best partner (mode="all": every such pair; splits and merges fuse).
+        images: a sequence of Z images of one size or an array [Z, H, W, 3], in the dtypes of generate().  -> (volume int32 [Z, H, W] on the
+        model's device, records, objects): the planes' records concatenated in plane order, each with "plane" and "object" = its id in `volume`
+        (0: hidden in its plane, or its object was dropped by min_planes / min_volume); "label" stays the record's id in its own plane's label
+        map.  objects = {"voxels" int64 [K], "zrange" int32 [K, 2], "boxes" int32 [K, 4], "label_of_global" int32 [G + 1]} as link_label_stack
+        returns them (utils.stack.track_table(label_of_global, counts) turns the last into the [K, Z] index of per-plane labels).
+        A stack of one plane returns that plane's generate_label_map labels exactly.
+        Not done here: an object missing from a plane is not bridged (it comes back as a new object), divisions are no events, planes are not
+        sharded over ranks, and the whole label stack has to fit in device memory."""
+        from .utils import stack as K
+        if isinstance(images, (np.ndarray, torch.Tensor)) and images.ndim != 4:
+            raise ValueError(f"generate_stack_label_volume: an array of images must be [Z, H, W, 3], got {tuple(images.shape)}")
+        if len(images) < 1:
+            raise ValueError("generate_stack_label_volume: no planes")
+        dev = self.model.device
+        planes, records, counts = None, [], []
+        for z in range(len(images)):
+            labels_z, recs = self.generate_label_map(images[z], order=order, min_visible_area=min_visible_area)
+            if planes is None:
+                planes = torch.empty((len(images),) + tuple(labels_z.shape), dtype=torch.int32, device=dev)
+            elif tuple(labels_z.shape) != tuple(planes.shape[1:]):
+                raise ValueError(f"generate_stack_label_volume: plane {z} is {tuple(labels_z.shape)}, plane 0 is {tuple(planes.shape[1:])}")
+            planes[z].copy_(labels_z)
+            counts.append(max((r["label"] for r in recs), default=0))            # the plane's labels are 1..K_z
+            for r in recs:
+                r["plane"] = z
+            records.append(recs)
+        volume, label_of_global, voxels, zrange, boxes = K.link_label_stack(planes, counts, iou=iou, mode=mode, min_planes=min_planes,
+                                                                            min_volume=min_volume, device=dev)
+        lut = label_of_global.cpu().numpy()
+        base = np.concatenate([[0], np.cumsum(counts)])
+        out = []
+        for z, recs in enumerate(records):
+            for r in recs:
+                r["object"] = int(lut[base[z] + r["label"]]) if r["label"] else 0
+                out.append(r)
+        return volume, out, {"voxels": voxels, "zrange": zrange, "boxes": boxes, "label_of_global": label_of_global}

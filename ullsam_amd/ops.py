@@ -987,6 +987,132 @@ def mosaic_paste(tiles: torch.Tensor, base: torch.Tensor, g: int, cores: torch.T
     return out
 
 
+# ---- per-plane label maps linked into 3-D objects (csrc/stack.hip; utils.stack drives these) --------------------------------------------------
+STACK_MAX_PLANES = 65535
+STACK_MAX_SIDE = 46340    # H * W < 2^31: an area, an overlap and a union fit 32 bits, n * u fits unsigned 64
+STACK_FLAGS = 4           # bad id / table entry, table overflow, distinct pairs, (free: utils.stack keeps K there)
+
+
+def _stack_planes(planes: torch.Tensor, base: torch.Tensor, g: int):
+    _chk(planes, "planes", torch.int32); _chk(base, "base", torch.int32)
+    assert planes.dim() == 3 and base.numel() == planes.shape[0] + 1, (tuple(planes.shape), base.numel())
+    z, h, w = planes.shape
+    if not (1 <= z <= STACK_MAX_PLANES and 1 <= h <= STACK_MAX_SIDE and 1 <= w <= STACK_MAX_SIDE):
+        raise _lib.UllsamError(f"stack: planes {tuple(planes.shape)} must be [1..{STACK_MAX_PLANES}, 1..{STACK_MAX_SIDE}, 1..{STACK_MAX_SIDE}]")
+    if not 0 <= int(g) <= MOSAIC_MAX_IDS:
+        raise _lib.UllsamError(f"stack: g = {g} must lie in 0..2^31 - 2")
+    return z, h, w
+
+
+def _stack_iou(iou, what: str):
+    num, den = (int(v) for v in iou)
+    if not (0 < num <= den < 2 ** 31):
+        raise _lib.UllsamError(f"{what}: iou = (num, den) needs 0 < num <= den < 2^31, got {(num, den)}")
+    return num, den
+
+
+def _stack_flags(flags: Optional[torch.Tensor], dev) -> torch.Tensor:
+    return torch.zeros((STACK_FLAGS,), dtype=torch.int32, device=dev) if flags is None else _out_i32(flags, (STACK_FLAGS,), dev, "flags")
+
+
+def stack_pairs(planes: torch.Tensor, base: torch.Tensor, g: int, max_pairs: int, flags: Optional[torch.Tensor] = None):
+    """planes int32 [Z, H, W], base int32 [Z + 1] (exclusive sum of the planes' id counts, g = base[Z]) -> (keys int64 [slots] -- g_a << 32 | g_b,
+    a in plane z and b in plane z + 1, 0 = empty --, counts int32 [slots], areas int32 [g + 1], flags int32 [4]); the caller reads flags."""
+    z, h, w = _stack_planes(planes, base, g)
+    assert max_pairs >= 1
+    dev = planes.device
+    cap = mosaic_table_slots(max_pairs)
+    keys = torch.empty((cap,), dtype=torch.int64, device=dev)
+    counts = torch.empty((cap,), dtype=torch.int32, device=dev)
+    areas = torch.empty((g + 1,), dtype=torch.int32, device=dev)
+    flags = _out_i32(flags, (STACK_FLAGS,), dev, "flags")
+    _lib.call("ullsam_stack_pairs", planes.data_ptr(), z, h, w, base.data_ptr(), int(g), keys.data_ptr(), counts.data_ptr(), cap, int(max_pairs),
+              areas.data_ptr(), flags.data_ptr(), _stream())
+    return keys, counts, areas, flags
+
+
+def _stack_table(keys: torch.Tensor, counts: torch.Tensor, areas: torch.Tensor, g: int):
+    _chk(keys, "keys", torch.int64); _chk(counts, "counts", torch.int32); _chk(areas, "areas", torch.int32)
+    assert counts.numel() == keys.numel() and areas.numel() == g + 1 and 0 <= g <= MOSAIC_MAX_IDS
+
+
+def stack_best(keys: torch.Tensor, counts: torch.Tensor, areas: torch.Tensor, g: int, iou=(1, 4), flags: Optional[torch.Tensor] = None):
+    """A pair table (stack_pairs' outputs, or hand-made: keys int64 [n], counts int32 [n], areas int32 [g + 1]) -> (succ int32 [g + 1], pred int32
+    [g + 1], flags): the partner of every id's best candidate in the next / the previous plane, 0 where it has none (ullsam_hip.h stack_best)."""
+    _stack_table(keys, counts, areas, g)
+    num, den = _stack_iou(iou, "stack_best")
+    succ = torch.empty((g + 1,), dtype=torch.int32, device=keys.device)
+    pred = torch.empty((g + 1,), dtype=torch.int32, device=keys.device)
+    flags = _stack_flags(flags, keys.device)
+    _lib.call("ullsam_stack_best", keys.data_ptr(), counts.data_ptr(), keys.numel(), areas.data_ptr(), int(g), num, den, succ.data_ptr(), pred.data_ptr(),
+              flags.data_ptr(), _stream())
+    return succ, pred, flags
+
+
+def stack_link(g: int, succ: Optional[torch.Tensor] = None, pred: Optional[torch.Tensor] = None, keys: Optional[torch.Tensor] = None,
+               counts: Optional[torch.Tensor] = None, areas: Optional[torch.Tensor] = None, iou=(1, 4), flags: Optional[torch.Tensor] = None):
+    """-> (parent int32 [g + 1]: the smallest id of every id's object, flags).  With succ / pred (stack_best's): the mutual links, objects are chains.
+    With keys / counts / areas instead: every candidate of the table is a link."""
+    assert (succ is None) == (pred is None) and (succ is None) != (keys is None)
+    num, den = _stack_iou(iou, "stack_link")
+    if succ is not None:
+        _chk(succ, "succ", torch.int32); _chk(pred, "pred", torch.int32)
+        assert succ.numel() == g + 1 and pred.numel() == g + 1 and 0 <= g <= MOSAIC_MAX_IDS
+        dev, n = succ.device, 0
+    else:
+        _stack_table(keys, counts, areas, g)
+        dev, n = keys.device, keys.numel()
+    parent = torch.empty((g + 1,), dtype=torch.int32, device=dev)
+    flags = _stack_flags(flags, dev)
+    _lib.call("ullsam_stack_link", _p(succ), _p(pred), _p(keys), _p(counts), n, _p(areas), int(g), num, den, parent.data_ptr(), flags.data_ptr(), _stream())
+    return parent, flags
+
+
+def stack_stats(planes: torch.Tensor, base: torch.Tensor, g: int, parent: torch.Tensor, flags: Optional[torch.Tensor] = None):
+    """parent as stack_link leaves it -> (voxels_raw int64 [g + 1], zrange_raw int32 [g + 1, 2], boxes_raw int32 [g + 1, 4] inclusive XYXY, flags) per
+    representative."""
+    z, h, w = _stack_planes(planes, base, g)
+    _chk(parent, "parent", torch.int32)
+    assert parent.numel() == g + 1
+    dev = planes.device
+    voxels = torch.empty((g + 1,), dtype=torch.int64, device=dev)
+    zrange = torch.empty((g + 1, 2), dtype=torch.int32, device=dev)
+    boxes = torch.empty((g + 1, 4), dtype=torch.int32, device=dev)
+    flags = _stack_flags(flags, dev)
+    _lib.call("ullsam_stack_stats", planes.data_ptr(), z, h, w, base.data_ptr(), int(g), parent.data_ptr(), voxels.data_ptr(), zrange.data_ptr(),
+              boxes.data_ptr(), flags.data_ptr(), _stream())
+    return voxels, zrange, boxes, flags
+
+
+def stack_compact(voxels_raw: torch.Tensor, zrange_raw: torch.Tensor, boxes_raw: torch.Tensor, parent: torch.Tensor, min_planes: int = 1,
+                  min_volume: int = 0, k_out: Optional[torch.Tensor] = None):
+    """-> (label_of_global int32 [g + 1], voxels int64 [g], zrange int32 [g, 2], boxes int32 [g, 4] -- their first K entries are the final objects' --,
+    K int32 [1])."""
+    _chk(voxels_raw, "voxels_raw", torch.int64); _chk(zrange_raw, "zrange_raw", torch.int32); _chk(boxes_raw, "boxes_raw", torch.int32)
+    _chk(parent, "parent", torch.int32)
+    g = parent.numel() - 1
+    assert g >= 0 and voxels_raw.numel() == g + 1 and zrange_raw.numel() == 2 * (g + 1) and boxes_raw.numel() == 4 * (g + 1)
+    dev = parent.device
+    log = torch.empty((g + 1,), dtype=torch.int32, device=dev)
+    voxels = torch.zeros((g,), dtype=torch.int64, device=dev)
+    zrange = torch.zeros((g, 2), dtype=torch.int32, device=dev)
+    boxes = torch.zeros((g, 4), dtype=torch.int32, device=dev)
+    k_out = _out_i32(k_out, (1,), dev, "k_out")
+    _lib.call("ullsam_stack_compact", voxels_raw.data_ptr(), zrange_raw.data_ptr(), boxes_raw.data_ptr(), parent.data_ptr(), g, int(min_planes),
+              int(min_volume), log.data_ptr(), voxels.data_ptr(), zrange.data_ptr(), boxes.data_ptr(), k_out.data_ptr(), _stream())
+    return log, voxels, zrange, boxes, k_out
+
+
+def stack_relabel(planes: torch.Tensor, base: torch.Tensor, g: int, label_of_global: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """volume int32 [Z, H, W]: every plane copied through label_of_global."""
+    z, h, w = _stack_planes(planes, base, g)
+    _chk(label_of_global, "label_of_global", torch.int32)
+    assert label_of_global.numel() == g + 1
+    out = _out_i32(out, (z, h, w), planes.device, "out")
+    _lib.call("ullsam_stack_relabel", planes.data_ptr(), z, h, w, base.data_ptr(), int(g), label_of_global.data_ptr(), out.data_ptr(), _stream())
+    return out
+
+
 # ---- per-instance measurements and contacts from a label image (csrc/measure.hip; utils.measure drives these) ---------------------------------
 MEASURE_MAX_SIDE = 46340  # x * x < 2^31 and H * W < 2^31: every sum of the tables stays below 2^62
 MEASURE_MAX_CHANNELS = 4

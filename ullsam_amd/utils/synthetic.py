@@ -82,6 +82,34 @@ def label_frame(seed: int, height: int, width: int, n_cells: int, r_range: Tuple
     return labels
 
 
+def label_stack(seed: int, Z: int, H: int, W: int, n_cells: int, r_range: Tuple[float, float], dz: float):
+    """-> (planes int32 [Z, H, W], counts): spheres ("cells" in a z-stack) cut by Z planes dz apart (in pixels), every plane numbering the
+    cells IT sees 1..K_z by a permutation of its own, so that the same cell carries unrelated ids in neighbouring planes and linking by
+    identity cannot pass a test.  Centres uniform over the frame and over (-1, Z) planes, radii uniform over r_range; plane z cuts cell i in
+    the disc (x - cx)^2 + (y - cy)^2 <= r^2 - (dz (z - cz))^2 (float64), later cells on top; a cell that later cells hide leaves its id absent."""
+    rng = np.random.default_rng([int(seed), 0x57AC])
+    cx = rng.uniform(0, W, n_cells)
+    cy = rng.uniform(0, H, n_cells)
+    cz = rng.uniform(-1, Z, n_cells)
+    r = rng.uniform(r_range[0], r_range[1], n_cells)
+    planes = np.zeros((Z, H, W), np.int32)
+    counts = []
+    for z in range(Z):
+        rr2 = r ** 2 - (dz * (z - cz)) ** 2
+        present = np.nonzero(rr2 > 0)[0]
+        perm = rng.permutation(len(present))
+        for j, i in enumerate(present):                  # (the disc test runs inside the disc's bounding box only: the same pixels, fewer tests)
+            rad = math.sqrt(rr2[i])
+            y0, y1 = max(int(math.floor(cy[i] - rad)) - 1, 0), min(int(math.ceil(cy[i] + rad)) + 2, H)
+            x0, x1 = max(int(math.floor(cx[i] - rad)) - 1, 0), min(int(math.ceil(cx[i] + rad)) + 2, W)
+            if y0 >= y1 or x0 >= x1:
+                continue
+            yy, xx = np.mgrid[y0:y1, x0:x1].astype(np.float64)
+            planes[z, y0:y1, x0:x1][(xx - cx[i]) ** 2 + (yy - cy[i]) ** 2 <= rr2[i]] = perm[j] + 1
+        counts.append(len(present))
+    return planes, counts
+
+
 def param_init_rule(name: str, shape) -> Tuple[float, float]:
     """(mean, std) of the normal distribution bench.py draws parameter `name` from: the same per-name table the reference-generated
     fixtures were filled with (oracle/ullsam_oracle.py::fill_param; tests/test_host_cpu.py checks the two agree), so the bench runs on
