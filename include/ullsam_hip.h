@@ -452,6 +452,27 @@ int ullsam_stack_stats(const int* planes, int Z, int H, int W, const int* base, 
 int ullsam_stack_compact(const long* voxels_raw, const int* zrange_raw, const int* boxes_raw, const int* parent, long G, int min_planes,
                          long min_volume, int* label_of_global, long* voxels, int* zrange, int* boxes, int* K, void* stream);
 int ullsam_stack_relabel(const int* planes, int Z, int H, int W, const int* base, long G, const int* label_of_global, int* volume, void* stream);
+/* Exact squared Euclidean distance transforms of a label image (csrc/distance.hip; integer work, bit-exact with the host forms of
+   utils.distance; definition in DESIGN.md "7b, continued (distances)").  labels i32 [H, W], 0 = background, 1 <= H, W <= 32767.  INF = 2^31 - 1;
+   in the 16-bit column maps 0xFFFF says "none".  flags i32 [4]: [0] = 1 when a label is negative or above K (the pixel is skipped, nothing is
+   indexed with it); the entries only ever set it, the caller zeroes it.
+   distance_columns: feature = 0: g u16 [H, W] = the vertical distance from a labelled pixel to the nearest pixel of its column with another
+     label (the pixels just outside the frame count when edge is set; 0xFFFF at an open frame end; 0 on the background), nearest is not
+     touched.  feature = 1: g = the vertical distance to the nearest labelled pixel of the column (0xFFFF: the column has none), nearest
+     i32 [H, W] = its label, the smaller of the two at equal distance above and below (0 with 0xFFFF).
+   distance_rows: the row pass over distance_columns' maps (feature = 0 for the modes 0, 3, 4; feature = 1 for 1, 2).  mode 0: out0 = D2, the
+     squared distance of every labelled pixel to the nearest pixel with another label (0 on the background); 1: out0 = D2 to the nearest
+     labelled pixel, out1 = the smallest label among the pixels that attain it, both (INF, 0) where D2 > limit; 2: out0 = the label, or on the
+     background the nearest label where D2 <= limit, else 0; 3: out0 = the label where its D2 > limit, else 0; 4: best u64 [K] is zeroed and
+     takes per label the maximum of D2 << 32 | (0xFFFFFFFF - linear index) over its pixels.  limit in 0..INF; the modes 0 and 4 need INF.  No
+     scan looks farther than floor(sqrt(limit)) columns (W when limit = INF).  route 0: that reach <= 128 stages the row segment in LDS,
+     a longer one reads global memory; 1: LDS (an error beyond 128); 2: global memory.  The outputs do not depend on the route.
+   distance_depth_decode: r2 i32 [K] = best >> 32, xy i32 [K, 2] = (x, y) of the linear index; a zero word (an absent id) gives 0, (-1, -1). */
+int ullsam_distance_columns(const int* labels, int H, int W, int feature, int edge, long K, unsigned short* g, int* nearest, int* flags,
+                            void* stream);
+int ullsam_distance_rows(const int* labels, const unsigned short* g, const int* nearest, int H, int W, int mode, int edge, long limit, int route,
+                         long K, int* out0, int* out1, unsigned long long* best, int* flags, void* stream);
+int ullsam_distance_depth_decode(const unsigned long long* best, long K, int W, int* r2, int* xy, void* stream);
 /* Per-instance measurements and contacts from a label image (csrc/measure.hip; integer work, bit-exact with the host forms
    utils.measure.measure_instances / label_contacts; definition in DESIGN.md "7b, continued: measurements").  labels i32 [H, W] with ids
    0..K, 0 = background, 1 <= H, W <= 46340 (x * x and every area stay below 2^31, every sum below 2^62), K <= 2^31 - 2.  Row k - 1 of every

@@ -42,7 +42,9 @@ HOT_LABELS = [r"rle_paint_kernel", r"label_stats_init_kernel", r"label_stats_ker
               r"resize_nearest_i32_kernel"]
 # per-instance measurements and contacts from a label image (csrc/measure.hip)
 HOT_MEASURE = [r"measure_kernelILi\dE", r"contacts_kernel"]
-HOT_BF16 = HOT_BF16 + HOT_AMG + HOT_REGIONS + HOT_DECODE_FP8 + HOT_LABELS + HOT_MEASURE
+# exact distance transforms of a label image (csrc/distance.hip): the column pass, every route and mode of the row pass, the depth decode
+HOT_DISTANCE = [r"dist_columns_kernelILb[01]E", r"dist_rows_kernelILb[01]ELi\dE", r"dist_depth_decode_kernel"]
+HOT_BF16 = HOT_BF16 + HOT_AMG + HOT_REGIONS + HOT_DECODE_FP8 + HOT_LABELS + HOT_MEASURE + HOT_DISTANCE
 HOT = HOT_BF16
 # round 6: the persistent ring kernel (<MI0, MI1, NTW, EMODE, STAMP = false>: the six shapes without stamps): no spilled VECTOR register and no scratch.  Its tile loop keeps more scalars than the 102 SGPRs hold
 # (tile coordinates, two buffer descriptors, the kernel arguments the epilogue reads): hipcc parks the overflow in lanes of a VGPR (v_writelane / v_readlane, outside the K loop) -- counted as

@@ -109,6 +109,9 @@ SIGNATURES = {
     "ullsam_stack_stats": [vp, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp],
     "ullsam_stack_compact": [vp, vp, vp, vp, i64, i32, i64, vp, vp, vp, vp, vp, vp],
     "ullsam_stack_relabel": [vp, i32, i32, i32, vp, i64, vp, vp, vp],
+    "ullsam_distance_columns": [vp, i32, i32, i32, i32, i64, vp, vp, vp, vp],
+    "ullsam_distance_rows": [vp, vp, vp, i32, i32, i32, i32, i64, i32, i64, vp, vp, vp, vp, vp],
+    "ullsam_distance_depth_decode": [vp, i64, i32, vp, vp, vp],
     "ullsam_measure_instances": [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "ullsam_label_contacts": [vp, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp],
     "ullsam_label_d1": [vp, i32, i32, i32, vp, vp, vp, vp],

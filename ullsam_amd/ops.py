@@ -1113,6 +1113,89 @@ def stack_relabel(planes: torch.Tensor, base: torch.Tensor, g: int, label_of_glo
     return out
 
 
+# ---- exact squared Euclidean distance transforms of a label image (csrc/distance.hip; utils.distance drives these) ----------------------------
+DISTANCE_MAX_SIDE = 32767  # every finite squared distance <= 2 * 32766^2 < 2^31 - 1
+DISTANCE_INF = 2 ** 31 - 1
+DISTANCE_INF16 = 0xFFFF    # "none" in the 16-bit column maps
+DISTANCE_LDS_HALO = 128    # the row pass stages its segment in LDS while floor(sqrt(limit)) <= this
+DISTANCE_FLAGS = 4         # bad id, (three free)
+DISTANCE_MODES = {"inner": 0, "feature": 1, "expand": 2, "shrink": 3, "depth": 4}
+DISTANCE_ROUTES = {"auto": 0, "lds": 1, "global": 2}
+
+
+def _distance_frame(labels: torch.Tensor, num, what: str):
+    _chk(labels, "labels", torch.int32)
+    assert labels.dim() == 2, tuple(labels.shape)
+    h, w = labels.shape
+    if not (1 <= h <= DISTANCE_MAX_SIDE and 1 <= w <= DISTANCE_MAX_SIDE):
+        raise _lib.UllsamError(f"{what}: a frame of {h} x {w} (each side must lie in 1..{DISTANCE_MAX_SIDE})")
+    k = DISTANCE_INF if num is None else int(num)
+    if not 0 <= k <= DISTANCE_INF:
+        raise _lib.UllsamError(f"{what}: num = {num} must lie in 0..2^31 - 1")
+    return h, w, k
+
+
+def _distance_flags(flags: Optional[torch.Tensor], dev) -> torch.Tensor:
+    return torch.zeros((DISTANCE_FLAGS,), dtype=torch.int32, device=dev) if flags is None else _out_i32(flags, (DISTANCE_FLAGS,), dev, "flags")
+
+
+def distance_columns(labels: torch.Tensor, feature: bool = False, edge: bool = False, num: Optional[int] = None, flags: Optional[torch.Tensor] = None):
+    """labels int32 [H, W] -> (g uint16 [H, W], nearest int32 [H, W] or None, flags): the column pass (ullsam_hip.h distance_columns).  feature False: g =
+    the vertical distance of a labelled pixel to the nearest pixel of its column with another label; True: to the nearest labelled pixel, whose
+    label is `nearest`.  0xFFFF = none.  flags (zeroed by the caller, or made here): [0] = a label below 0 or above num."""
+    h, w, k = _distance_frame(labels, num, "distance_columns")
+    dev = labels.device
+    g = torch.empty((h, w), dtype=torch.uint16, device=dev)
+    nearest = torch.empty((h, w), dtype=torch.int32, device=dev) if feature else None
+    flags = _distance_flags(flags, dev)
+    _lib.call("ullsam_distance_columns", labels.data_ptr(), h, w, int(bool(feature)), int(bool(edge)), k, g.data_ptr(), _p(nearest), flags.data_ptr(), _stream())
+    return g, nearest, flags
+
+
+def distance_rows(labels: torch.Tensor, g: torch.Tensor, nearest: Optional[torch.Tensor], mode: str, edge: bool = False, limit: Optional[int] = None,
+                  route: str = "auto", num: Optional[int] = None, flags: Optional[torch.Tensor] = None):
+    """The row pass over distance_columns' maps (ullsam_hip.h distance_rows) -> (outputs, flags).  mode "inner": D2 int32 [H, W]; "feature": (D2, nearest
+    label), (INF, 0) beyond limit; "expand": the labels grown by limit = r2; "shrink": the labels whose D2 > limit = r2; "depth": best int64 [num]
+    (the bits of D2 << 32 | 0xFFFFFFFF - index; distance_depth_decode reads it).  limit None = unbounded (required for "inner" and "depth").  route
+    "auto" / "lds" / "global": where the scan reads from; the outputs do not depend on it."""
+    h, w, k = _distance_frame(labels, num, "distance_rows")
+    m = DISTANCE_MODES[mode]
+    feat = mode in ("feature", "expand")
+    dev = labels.device
+    _chk(g, "g", torch.uint16)
+    assert tuple(g.shape) == (h, w), tuple(g.shape)
+    if feat:
+        _chk(nearest, "nearest", torch.int32)
+        assert tuple(nearest.shape) == (h, w), tuple(nearest.shape)
+    lim = DISTANCE_INF if limit is None else int(limit)
+    if not 0 <= lim <= DISTANCE_INF:
+        raise _lib.UllsamError(f"distance_rows: limit = {limit} must lie in 0..2^31 - 1")
+    flags = _distance_flags(flags, dev)
+    out0 = out1 = best = None
+    if mode == "depth":
+        if num is None or k > MOSAIC_MAX_IDS:
+            raise _lib.UllsamError("distance_rows: the depths need num in 0..2^31 - 2")
+        best = torch.empty((k,), dtype=torch.int64, device=dev)
+    else:
+        out0 = torch.empty((h, w), dtype=torch.int32, device=dev)
+        if mode == "feature":
+            out1 = torch.empty((h, w), dtype=torch.int32, device=dev)
+    _lib.call("ullsam_distance_rows", labels.data_ptr(), g.data_ptr(), _p(nearest) if feat else None, h, w, m, int(bool(edge)), lim, DISTANCE_ROUTES[route], k,
+              _p(out0), _p(out1), _p(best), flags.data_ptr(), _stream())
+    out = best if mode == "depth" else ((out0, out1) if mode == "feature" else out0)
+    return out, flags
+
+
+def distance_depth_decode(best: torch.Tensor, w: int):
+    """best int64 [K] (distance_rows' "depth" output) of a frame of width w -> (r2 int32 [K], xy int32 [K, 2]); an absent id: 0 and (-1, -1)."""
+    _chk(best, "best", torch.int64)
+    k = best.numel()
+    r2 = torch.empty((k,), dtype=torch.int32, device=best.device)
+    xy = torch.empty((k, 2), dtype=torch.int32, device=best.device)
+    _lib.call("ullsam_distance_depth_decode", best.data_ptr(), k, int(w), r2.data_ptr(), xy.data_ptr(), _stream())
+    return r2, xy
+
+
 # ---- per-instance measurements and contacts from a label image (csrc/measure.hip; utils.measure drives these) ---------------------------------
 MEASURE_MAX_SIDE = 46340  # x * x < 2^31 and H * W < 2^31: every sum of the tables stays below 2^62
 MEASURE_MAX_CHANNELS = 4
