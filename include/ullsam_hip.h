@@ -473,6 +473,37 @@ int ullsam_distance_columns(const int* labels, int H, int W, int feature, int ed
 int ullsam_distance_rows(const int* labels, const unsigned short* g, const int* nearest, int H, int W, int mode, int edge, long limit, int route,
                          long K, int* out0, int* out1, unsigned long long* best, int* flags, void* stream);
 int ullsam_distance_depth_decode(const unsigned long long* best, long K, int W, int* r2, int* xy, void* stream);
+/* Splitting the touching objects of a label image: a watershed of every instance's own depth map without a flood (csrc/split.hip; integer
+   work, bit-exact with the host form utils.split.split_labels; definition in DESIGN.md "7b, continued (splitting)").  labels i32 [H, W] with ids
+   0..K, 0 = background, 1 <= H, W <= 32767; d2 i32 [H, W] = distance_rows' mode 0 of the same labels; p = y * W + x, n = H * W;
+   key(p) = (d2[p], -p).  flags i32 [8], zeroed by the caller, only ever raised: [0] = a label below 0 or above K (the pixel counts as background)
+   or a hand-made table entry outside the frame (skipped), [1] = a pair was refused, [2] = the pairs claimed, [3] = a chain longer than
+   its bound, [4] = the representatives counted, [5] = the cursor of the list.
+   split_ascent: up i32 [H, W][p] = the pixel of greatest key among p and its 8 neighbours with p's label; p on the background.  route 0 / 1: a
+     workgroup stages its 64 x 4 pixels and a one-pixel halo in LDS; 2: global memory.  The output does not depend on the route.
+   split_flatten: up[p] = the root of p's chain (up[r] = r), in place, after at most `steps` <= n hops (flags[3] otherwise).
+   split_passes: keys u64 [cap] / vals i32 [cap]: the open-addressing pair table (cap a power of two >= 2 * max_pairs; both are zeroed here).  For
+     every 8-adjacent pixel pair of one label whose roots a < b differ (up flattened), vals of key a << 32 | b takes the maximum of
+     min(d2, d2).  Once more than max_pairs keys are held new ones are refused and flags[1] is set.
+   split_round: one round of merging over a pair table (cap slots, key 0 = empty; hand-made ones need no power of two) and flat maps of n
+     pixels.  Every edge whose ends lie in different components X = up[a] != Y = up[b] sends S << 32 | (0xFFFFFFFF - Y) to best[X] and the
+     mirrored word to best[Y] (u64 [n], zeroed by the caller once; the round leaves it zero again) with a 64-bit atomicMax; then every root X
+     with a word (S, Y) writes up[X] = Y and changed[0] = 1 when key(X) < key(Y) and, with t = d2[X] - S - h * h, t <= 0 or
+     t * t <= 4 * h * h * S (unsigned 64-bit).  0 <= h <= 32767.  The caller flattens before the next round.
+   split_collect: list = NULL: flags[4] += the number of representatives (up[p] = p on a labelled pixel); otherwise list u64 [room] takes
+     label << 32 | p of each, in no particular order, from flags[5] on while there is room.
+   split_relabel: list u64 [parts], sorted ascending.  Part i gets id i + 1: parent i32 [parts] = its label, peak_r2 i32 [parts] = d2 at its
+     representative, peak_xy i32 [parts, 2] = (x, y) of it, parts_of i32 [K] (zeroed here) counts the parts per label; newid i32 [H, W] is
+     scratch; out i32 [H, W][p] = the id of up[p]'s part, 0 on the background. */
+int ullsam_split_ascent(const int* labels, const int* d2, int H, int W, long K, int route, int* up, int* flags, void* stream);
+int ullsam_split_flatten(int* up, long n, long steps, int* flags, void* stream);
+int ullsam_split_passes(const int* labels, const int* d2, const int* up, int H, int W, long K, unsigned long long* keys, int* vals, long cap,
+                        int max_pairs, int* flags, void* stream);
+int ullsam_split_round(const unsigned long long* keys, const int* vals, long cap, const int* labels, const int* d2, long n, long K, int h,
+                       unsigned long long* best, int* up, int* changed, int* flags, void* stream);
+int ullsam_split_collect(const int* labels, const int* up, long n, long K, unsigned long long* list, long room, int* flags, void* stream);
+int ullsam_split_relabel(const unsigned long long* list, long parts, const int* labels, const int* d2, const int* up, int H, int W, long K,
+                         int* newid, int* out, int* parent, int* peak_r2, int* peak_xy, int* parts_of, int* flags, void* stream);
 /* Per-instance measurements and contacts from a label image (csrc/measure.hip; integer work, bit-exact with the host forms
    utils.measure.measure_instances / label_contacts; definition in DESIGN.md "7b, continued: measurements").  labels i32 [H, W] with ids
    0..K, 0 = background, 1 <= H, W <= 46340 (x * x and every area stay below 2^31, every sum below 2^62), K <= 2^31 - 2.  Row k - 1 of every

@@ -44,7 +44,10 @@ HOT_LABELS = [r"rle_paint_kernel", r"label_stats_init_kernel", r"label_stats_ker
 HOT_MEASURE = [r"measure_kernelILi\dE", r"contacts_kernel"]
 # exact distance transforms of a label image (csrc/distance.hip): the column pass, every route and mode of the row pass, the depth decode
 HOT_DISTANCE = [r"dist_columns_kernelILb[01]E", r"dist_rows_kernelILb[01]ELi\dE", r"dist_depth_decode_kernel"]
-HOT_BF16 = HOT_BF16 + HOT_AMG + HOT_REGIONS + HOT_DECODE_FP8 + HOT_LABELS + HOT_MEASURE + HOT_DISTANCE
+# splitting touching objects (csrc/split.hip): both routes of the ascent, flatten, passes, the two kernels of a round, collect, tables, relabel
+HOT_SPLIT = [r"split_ascent_kernelILb[01]E", r"split_flatten_kernel", r"split_passes_kernel", r"split_best_kernel", r"split_decide_kernel",
+             r"split_collect_kernel", r"split_tables_kernel", r"split_relabel_kernel"]
+HOT_BF16 = HOT_BF16 + HOT_AMG + HOT_REGIONS + HOT_DECODE_FP8 + HOT_LABELS + HOT_MEASURE + HOT_DISTANCE + HOT_SPLIT
 HOT = HOT_BF16
 # round 6: the persistent ring kernel (<MI0, MI1, NTW, EMODE, STAMP = false>: the six shapes without stamps): no spilled VECTOR register and no scratch.  Its tile loop keeps more scalars than the 102 SGPRs hold
 # (tile coordinates, two buffer descriptors, the kernel arguments the epilogue reads): hipcc parks the overflow in lanes of a VGPR (v_writelane / v_readlane, outside the K loop) -- counted as

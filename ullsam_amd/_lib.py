@@ -112,6 +112,12 @@ SIGNATURES = {
     "ullsam_distance_columns": [vp, i32, i32, i32, i32, i64, vp, vp, vp, vp],
     "ullsam_distance_rows": [vp, vp, vp, i32, i32, i32, i32, i64, i32, i64, vp, vp, vp, vp, vp],
     "ullsam_distance_depth_decode": [vp, i64, i32, vp, vp, vp],
+    "ullsam_split_ascent": [vp, vp, i32, i32, i64, i32, vp, vp, vp],
+    "ullsam_split_flatten": [vp, i64, i64, vp, vp],
+    "ullsam_split_passes": [vp, vp, vp, i32, i32, i64, vp, vp, i64, i32, vp, vp],
+    "ullsam_split_round": [vp, vp, i64, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp],
+    "ullsam_split_collect": [vp, vp, i64, i64, vp, i64, vp, vp],
+    "ullsam_split_relabel": [vp, i64, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp],
     "ullsam_measure_instances": [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "ullsam_label_contacts": [vp, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp],
     "ullsam_label_d1": [vp, i32, i32, i32, vp, vp, vp, vp],

@@ -414,7 +414,8 @@ class SamAutomaticMaskGenerator:
         return self._records(self._generate_data(image)[0], self.output_mode)
 
     @torch.no_grad()
-    def generate_label_map(self, image, order: str = "area", min_visible_area: int = 0, out_hw=None, window=None, measure: bool = False):
+    def generate_label_map(self, image, order: str = "area", min_visible_area: int = 0, out_hw=None, window=None, measure: bool = False,
+                           split_depth: Optional[int] = None):
         """Segment everything, then paint the records into ONE instance label image -- the file the app exports (app.py:688-707 save_instance,
         :807-826 export_mask) -- on the device (utils.amg.paint_label_map; csrc/labels.hip).  -> (labels int32 [H, W] on the model's device,
         records): the records are those of generate() with output_mode="uncompressed_rle", in the same order, each with one more key "label" = its
@@ -423,11 +424,19 @@ class SamAutomaticMaskGenerator:
         out_hw / window = (top, left, h, w): nearest resize of the label image and the part of it to return (the app's export resize and
         reverse_padding; utils.amg.resize_labels_nearest).
         measure=True: a third value, the utils.measure.InstanceTable of `labels` against the image, which must then be H x W x 3 uint8 (it is
-        uploaded once more, at 1 byte per sample); not with out_hw / window, after which the labels are no longer in the image's frame."""
+        uploaded once more, at 1 byte per sample); not with out_hw / window, after which the labels are no longer in the image's frame.
+        split_depth = h (an integer; None: nothing changes): the painted labels go through utils.split.split_labels(labels, min_depth=h) on the
+        device before anything else -- touching objects that came out as one record are cut at the necks of their distance map.  `labels` then
+        holds the parts, every record gains "parts" = the ids its pixels carry in `labels` (empty when the record is hidden) while "label" stays
+        its id before the split; out_hw / window and measure apply to the split labels."""
         if measure:
             if out_hw is not None or window is not None:
                 raise ValueError("generate_label_map: measure=True needs the labels in the image's frame (no out_hw / window)")
             _measure_image_check(image, "generate_label_map")
+        if split_depth is not None:
+            from .utils import split as SP
+            if isinstance(split_depth, bool) or not isinstance(split_depth, (int, np.integer)) or not 0 <= int(split_depth) <= SP.MAX_DEPTH:
+                raise ValueError(f"generate_label_map: split_depth must be None or an integer in 0..{SP.MAX_DEPTH}, got {split_depth!r}")
         data, orig_size = self._generate_data(image)
         records = self._records(data, "uncompressed_rle")
         keys = [r["predicted_iou"] for r in records] if order == "score" else None
@@ -435,11 +444,18 @@ class SamAutomaticMaskGenerator:
                                                     device=self.model.device, size=orig_size)
         for r, l in zip(records, of_record.cpu().tolist()):
             r["label"] = int(l)
+        num = len(areas)
+        if split_depth is not None:
+            parts = SP.split_labels(labels, min_depth=int(split_depth), num=num)
+            labels, num = parts.labels, int(parts.parent.numel())
+            first = np.concatenate([[0], np.cumsum(parts.parts_of.cpu().numpy())])                 # the parts of old id i: first[i - 1] + 1 .. first[i]
+            for r in records:
+                r["parts"] = list(range(int(first[r["label"] - 1]) + 1, int(first[r["label"]]) + 1)) if r["label"] else []
         if out_hw is not None or window is not None:
             labels = A.resize_labels_nearest(labels, tuple(labels.shape) if out_hw is None else out_hw, window)
         if measure:
             from .utils import measure as MS
-            return labels, records, MS.measure_instances(labels, torch.as_tensor(image), num=len(areas), device=labels.device)
+            return labels, records, MS.measure_instances(labels, torch.as_tensor(image), num=num, device=labels.device)
         return labels, records
 
     @torch.no_grad()

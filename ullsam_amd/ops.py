@@ -1196,6 +1196,112 @@ def distance_depth_decode(best: torch.Tensor, w: int):
     return r2, xy
 
 
+# ---- splitting the touching objects of a label image (csrc/split.hip; utils.split drives these) -----------------------------------------------
+SPLIT_FLAGS = 8            # bad id / entry, pair refused, pairs claimed, chain too long, representatives counted, list cursor, (two free)
+SPLIT_MAX_DEPTH = 32767
+SPLIT_ROUTES = {"auto": 0, "lds": 1, "global": 2}
+
+
+def _split_flags(flags: Optional[torch.Tensor], dev) -> torch.Tensor:
+    return torch.zeros((SPLIT_FLAGS,), dtype=torch.int32, device=dev) if flags is None else _out_i32(flags, (SPLIT_FLAGS,), dev, "flags")
+
+
+def _split_map(t: torch.Tensor, name: str, like: torch.Tensor, dtype=torch.int32):
+    _chk(t, name, dtype)
+    assert t.numel() == like.numel(), (name, tuple(t.shape), tuple(like.shape))
+
+
+def split_ascent(labels: torch.Tensor, d2: torch.Tensor, num: Optional[int] = None, route: str = "auto", flags: Optional[torch.Tensor] = None):
+    """labels, d2 int32 [H, W] (d2 = distance_rows' "inner" map) -> (up int32 [H, W], flags int32 [8]): up[p] = the linear index of the pixel of
+    greatest (d2, -index) among p and its 8 neighbours with p's label; p itself on the background (ullsam_hip.h split_ascent).  route "auto" /
+    "lds" / "global": where the 3 x 3 neighbourhood is read from; the output does not depend on it."""
+    h, w, k = _distance_frame(labels, num, "split_ascent")
+    _split_map(d2, "d2", labels)
+    flags = _split_flags(flags, labels.device)
+    up = torch.empty((h, w), dtype=torch.int32, device=labels.device)
+    _lib.call("ullsam_split_ascent", labels.data_ptr(), d2.data_ptr(), h, w, k, SPLIT_ROUTES[route], up.data_ptr(), flags.data_ptr(), _stream())
+    return up, flags
+
+
+def split_flatten(up: torch.Tensor, steps: Optional[int] = None, flags: Optional[torch.Tensor] = None):
+    """up int32, n pointers -> (up, flags): every pointer replaced, in place, by the root of its chain, after at most `steps` hops (default n)."""
+    _chk(up, "up", torch.int32)
+    n = up.numel()
+    flags = _split_flags(flags, up.device)
+    _lib.call("ullsam_split_flatten", up.data_ptr(), n, n if steps is None else int(steps), flags.data_ptr(), _stream())
+    return up, flags
+
+
+def split_passes(labels: torch.Tensor, d2: torch.Tensor, up: torch.Tensor, max_pairs: int, num: Optional[int] = None, flags: Optional[torch.Tensor] = None):
+    """up flattened -> (keys int64 [slots] -- smaller root << 32 | larger root, 0 = empty --, vals int32 [slots] = the pass: the largest min(d2, d2)
+    over the 8-adjacent pixel pairs of one label across the two basins, flags); the caller reads flags[1], flags[2]."""
+    h, w, k = _distance_frame(labels, num, "split_passes")
+    _split_map(d2, "d2", labels); _split_map(up, "up", labels)
+    max_pairs = int(max_pairs)
+    if not 1 <= max_pairs <= 2 ** 30:
+        raise _lib.UllsamError(f"split_passes: max_pairs must lie in 1..2^30, got {max_pairs}")
+    dev = labels.device
+    cap = mosaic_table_slots(max_pairs)
+    keys = torch.empty((cap,), dtype=torch.int64, device=dev)
+    vals = torch.empty((cap,), dtype=torch.int32, device=dev)
+    flags = _split_flags(flags, dev)
+    _lib.call("ullsam_split_passes", labels.data_ptr(), d2.data_ptr(), up.data_ptr(), h, w, k, keys.data_ptr(), vals.data_ptr(), cap, max_pairs,
+              flags.data_ptr(), _stream())
+    return keys, vals, flags
+
+
+def split_round(keys: torch.Tensor, vals: torch.Tensor, labels: torch.Tensor, d2: torch.Tensor, up: torch.Tensor, min_depth: int, best: torch.Tensor,
+                changed: torch.Tensor, num: Optional[int] = None, flags: Optional[torch.Tensor] = None):
+    """One round of merging (ullsam_hip.h split_round) over a pair table (split_passes', or hand-made: keys int64 [m], vals int32 [m]) and maps of n
+    pixels: up (flattened) gets up[X] = Y for every absorbed representative, changed int32 [1] is set to 1 when there is one.  best int64 [n] is
+    zero on entry and on return.  -> flags; the caller flattens `up` before the next round."""
+    _chk(keys, "keys", torch.int64); _chk(vals, "vals", torch.int32); _chk(labels, "labels", torch.int32)
+    _split_map(d2, "d2", labels); _split_map(up, "up", labels); _split_map(best, "best", labels, torch.int64)
+    _chk(changed, "changed", torch.int32)
+    assert vals.numel() == keys.numel() and changed.numel() >= 1
+    k = DISTANCE_INF if num is None else int(num)
+    h = int(min_depth)
+    if not (0 <= h <= SPLIT_MAX_DEPTH and 0 <= k <= DISTANCE_INF):
+        raise _lib.UllsamError(f"split_round: min_depth = {min_depth} must lie in 0..{SPLIT_MAX_DEPTH} and num in 0..2^31 - 1")
+    flags = _split_flags(flags, labels.device)
+    _lib.call("ullsam_split_round", keys.data_ptr(), vals.data_ptr(), keys.numel(), labels.data_ptr(), d2.data_ptr(), labels.numel(), k, h, best.data_ptr(),
+              up.data_ptr(), changed.data_ptr(), flags.data_ptr(), _stream())
+    return flags
+
+
+def split_collect(labels: torch.Tensor, up: torch.Tensor, parts: Optional[int] = None, num: Optional[int] = None, flags: Optional[torch.Tensor] = None):
+    """parts None: flags[4] += the number of representatives (up[p] = p on a labelled pixel) -> flags.  parts = that number: -> (list int64 [parts] =
+    label << 32 | p of every representative, in no particular order -- sorting it gives the order of the parts --, flags)."""
+    _chk(labels, "labels", torch.int32); _split_map(up, "up", labels)
+    k = DISTANCE_INF if num is None else int(num)
+    flags = _split_flags(flags, labels.device)
+    lst = None if parts is None else torch.zeros((int(parts),), dtype=torch.int64, device=labels.device)
+    _lib.call("ullsam_split_collect", labels.data_ptr(), up.data_ptr(), labels.numel(), k, _p(lst) if lst is not None and lst.numel() else None,
+              0 if lst is None else lst.numel(), flags.data_ptr(), _stream())
+    return flags if parts is None else (lst, flags)
+
+
+def split_relabel(parts_sorted: torch.Tensor, labels: torch.Tensor, d2: torch.Tensor, up: torch.Tensor, num: int, flags: Optional[torch.Tensor] = None):
+    """parts_sorted int64 [K'] (split_collect's list, sorted), up flattened -> (out int32 [H, W], parent int32 [K'], peak_r2 int32 [K'], peak_xy
+    int32 [K', 2], parts_of int32 [num], flags): part i gets id i + 1 (ullsam_hip.h split_relabel)."""
+    h, w, k = _distance_frame(labels, num, "split_relabel")
+    _chk(parts_sorted, "parts_sorted", torch.int64); _split_map(d2, "d2", labels); _split_map(up, "up", labels)
+    if k > MOSAIC_MAX_IDS:
+        raise _lib.UllsamError("split_relabel: num must lie in 0..2^31 - 2")
+    dev = labels.device
+    n = parts_sorted.numel()
+    out = torch.empty((h, w), dtype=torch.int32, device=dev)
+    newid = torch.empty((h, w), dtype=torch.int32, device=dev)
+    parent = torch.empty((n,), dtype=torch.int32, device=dev)
+    peak_r2 = torch.empty((n,), dtype=torch.int32, device=dev)
+    peak_xy = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    parts_of = torch.empty((k,), dtype=torch.int32, device=dev)
+    flags = _split_flags(flags, dev)
+    _lib.call("ullsam_split_relabel", _p(parts_sorted) if n else None, n, labels.data_ptr(), d2.data_ptr(), up.data_ptr(), h, w, k, newid.data_ptr(),
+              out.data_ptr(), parent.data_ptr(), peak_r2.data_ptr(), peak_xy.data_ptr(), _p(parts_of) if k else None, flags.data_ptr(), _stream())
+    return out, parent, peak_r2, peak_xy, parts_of, flags
+
+
 # ---- per-instance measurements and contacts from a label image (csrc/measure.hip; utils.measure drives these) ---------------------------------
 MEASURE_MAX_SIDE = 46340  # x * x < 2^31 and H * W < 2^31: every sum of the tables stays below 2^62
 MEASURE_MAX_CHANNELS = 4
