@@ -504,6 +504,46 @@ int ullsam_split_round(const unsigned long long* keys, const int* vals, long cap
 int ullsam_split_collect(const int* labels, const int* up, long n, long K, unsigned long long* list, long room, int* flags, void* stream);
 int ullsam_split_relabel(const unsigned long long* list, long parts, const int* labels, const int* d2, const int* up, int H, int W, long K,
                          int* newid, int* out, int* parent, int* peak_r2, int* peak_xy, int* parts_of, int* flags, void* stream);
+/* Outlines of a label image: every instance as closed polygon loops on the pixel lattice (csrc/outline.hip; integer work, bit-exact with the
+   host form utils.outline.label_outlines; definition in DESIGN.md "7b, continued (outlines)").  labels i32 [H, W] with ids 0..K, 0 =
+   background, 1 <= H, W and n = H * W < 2^29; p = y * W + x.  Side s of a pixel of label k > 0 whose 4-neighbour is not k (the frame's outside
+   included) is a directed unit edge with the instance on its right: 0 = top (east), 1 = right (south), 2 = bottom (west), 3 = left (north); its
+   id is 4 * p + s, its compact index its position among the E edges in id order.  flags i32 [8], zeroed by the caller, only ever raised: [0] = a
+   label below 0 or above K (the pixel counts as background) or an index of a hand-made table outside its range (skipped), [1] = E, [2] = the
+   corners, [3] = the leaders, [4] = the cursor of the list, [5] = a parent chain longer than L.
+   outline_sides: mask u8 [n]: bit s = side s is an edge; off i32 [n] = the exclusive scan of popcount(mask), so edge (p, s) has the compact index
+     off[p] + popcount(mask[p] & ((1 << s) - 1)); flags[1] = E.  sums i32 [ceil(n / 2048)] is scratch.
+   outline_scan: off i32 [n] = the exclusive scan of (vals[i] != 0) over vals u8 [n], total[0] = their number; sums as above.
+   outline_successors: eid i32 [E] = the edge ids; succ i32 [E] = the compact index of the edge of the same label that starts at the head.  With
+     AL / AR the pixels ahead-left / ahead-right of the head: connectivity 8 turns left when AL == k, else goes straight when AR == k, else turns
+     right; connectivity 4 turns right unless AR == k, and then left when AL == k too, else straight.  Left: side (s + 3) % 4 of AL; straight: side
+     s of AR; right: side (s + 1) % 4 of the same pixel.  pdir u8 [E][succ[e]] = the side of e.
+   outline_rank: ws i32 [2, E, 4], aligned to 16 bytes, is scratch (the words (mn, pos, jump, 0) of every edge, twice); `rounds` = ceil(log2 E)
+     rounds of pointer doubling, never in place.  leader i32 [E] = the smallest compact index on e's cycle, rank i32 [E] = the steps from the
+     leader to e.  flags[3] += the leaders (leader[e] = e), flags[2] += the corners (pdir[e] != eid[e] & 3).
+   outline_collect: list u64 [room] takes labels[eid[e] >> 2] << 32 | e of every leader, in no particular order, from flags[4] on.
+   outline_loops: loop_of i32 [E] holds, at every leader, the index of its loop in 0..L - 1.  edges i32 [L] = the edges of every loop, area2
+     i64 [L] = the sum of x_t * y_h - x_h * y_t over them (tail t, head h): > 0 an outer loop, < 0 a hole.  Both are zeroed here.
+   outline_order: estart i32 [L] = the exclusive scan of `edges`.  Slot estart[loop of e] + rank[e] of reid i32 [E] / corner u8 [E] takes eid[e] /
+     (pdir[e] != eid[e] & 3): the edges loop after loop, each in travel order from its leader.
+   outline_vertices: coff = outline_scan of corner; vertices i32 [N, 2][coff[i]] = the tail (x, y) of reid[i] where corner[i].
+   outline_parents: lead i32 [L] = the compact index of every loop's leader.  parent i32 [L][i] = i for an outer loop; a hole walks left from its
+     leader's pixel while the label lasts, takes the loop of that pixel's left side, and repeats from that loop's leader until area2 > 0. */
+int ullsam_outline_sides(const int* labels, int H, int W, long K, unsigned char* mask, int* off, int* sums, int* flags, void* stream);
+int ullsam_outline_scan(const unsigned char* vals, long n, int* off, int* sums, int* total, void* stream);
+int ullsam_outline_successors(const int* labels, int H, int W, const unsigned char* mask, const int* off, long E, int connectivity, int* eid,
+                              int* succ, unsigned char* pdir, int* flags, void* stream);
+int ullsam_outline_rank(const int* succ, const int* eid, const unsigned char* pdir, long E, int rounds, int* ws, int* leader, int* rank, int* flags,
+                        void* stream);
+int ullsam_outline_collect(const int* labels, long n, const int* eid, const int* leader, long E, unsigned long long* list, long room, int* flags,
+                           void* stream);
+int ullsam_outline_loops(const int* eid, const int* leader, const int* loop_of, long E, long L, int W, int* edges, long long* area2, int* flags,
+                         void* stream);
+int ullsam_outline_order(const int* eid, const unsigned char* pdir, const int* leader, const int* rank, const int* loop_of, const int* estart, long E,
+                         long L, int* reid, unsigned char* corner, int* flags, void* stream);
+int ullsam_outline_vertices(const int* reid, const unsigned char* corner, const int* coff, long E, int W, long N, int* vertices, void* stream);
+int ullsam_outline_parents(const int* labels, int H, int W, const unsigned char* mask, const int* off, const int* eid, const int* leader,
+                           const int* loop_of, const int* lead, const long long* area2, long E, long L, int* parent, int* flags, void* stream);
 /* Per-instance measurements and contacts from a label image (csrc/measure.hip; integer work, bit-exact with the host forms
    utils.measure.measure_instances / label_contacts; definition in DESIGN.md "7b, continued: measurements").  labels i32 [H, W] with ids
    0..K, 0 = background, 1 <= H, W <= 46340 (x * x and every area stay below 2^31, every sum below 2^62), K <= 2^31 - 2.  Row k - 1 of every

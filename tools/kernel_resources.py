@@ -47,7 +47,12 @@ HOT_DISTANCE = [r"dist_columns_kernelILb[01]E", r"dist_rows_kernelILb[01]ELi\dE"
 # splitting touching objects (csrc/split.hip): both routes of the ascent, flatten, passes, the two kernels of a round, collect, tables, relabel
 HOT_SPLIT = [r"split_ascent_kernelILb[01]E", r"split_flatten_kernel", r"split_passes_kernel", r"split_best_kernel", r"split_decide_kernel",
              r"split_collect_kernel", r"split_tables_kernel", r"split_relabel_kernel"]
-HOT_BF16 = HOT_BF16 + HOT_AMG + HOT_REGIONS + HOT_DECODE_FP8 + HOT_LABELS + HOT_MEASURE + HOT_DISTANCE + HOT_SPLIT
+# outlines of a label image (csrc/outline.hip): side masks, the three kernels of the scan in both forms, successors, the doubling, the loop tables,
+# the ordered compaction, parents
+HOT_OUTLINE = [r"outline_sides_kernel", r"outline_sums_kernelILb[01]E", r"outline_scan_sums_kernel", r"outline_offsets_kernelILb[01]E",
+               r"outline_successors_kernel", r"outline_rank_init_kernel", r"outline_rank_round_kernel", r"outline_rank_finish_kernel",
+               r"outline_collect_kernel", r"outline_loops_kernel", r"outline_order_kernel", r"outline_vertices_kernel", r"outline_parents_kernel"]
+HOT_BF16 = HOT_BF16 + HOT_AMG + HOT_REGIONS + HOT_DECODE_FP8 + HOT_LABELS + HOT_MEASURE + HOT_DISTANCE + HOT_SPLIT + HOT_OUTLINE
 HOT = HOT_BF16
 # round 6: the persistent ring kernel (<MI0, MI1, NTW, EMODE, STAMP = false>: the six shapes without stamps): no spilled VECTOR register and no scratch.  Its tile loop keeps more scalars than the 102 SGPRs hold
 # (tile coordinates, two buffer descriptors, the kernel arguments the epilogue reads): hipcc parks the overflow in lanes of a VGPR (v_writelane / v_readlane, outside the K loop) -- counted as

@@ -118,6 +118,15 @@ SIGNATURES = {
     "ullsam_split_round": [vp, vp, i64, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp],
     "ullsam_split_collect": [vp, vp, i64, i64, vp, i64, vp, vp],
     "ullsam_split_relabel": [vp, i64, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp],
+    "ullsam_outline_sides": [vp, i32, i32, i64, vp, vp, vp, vp, vp],
+    "ullsam_outline_scan": [vp, i64, vp, vp, vp, vp],
+    "ullsam_outline_successors": [vp, i32, i32, vp, vp, i64, i32, vp, vp, vp, vp, vp],
+    "ullsam_outline_rank": [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp],
+    "ullsam_outline_collect": [vp, i64, vp, vp, i64, vp, i64, vp, vp],
+    "ullsam_outline_loops": [vp, vp, vp, i64, i64, i32, vp, vp, vp, vp],
+    "ullsam_outline_order": [vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp],
+    "ullsam_outline_vertices": [vp, vp, vp, i64, i32, i64, vp, vp],
+    "ullsam_outline_parents": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp],
     "ullsam_measure_instances": [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "ullsam_label_contacts": [vp, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp],
     "ullsam_label_d1": [vp, i32, i32, i32, vp, vp, vp, vp],

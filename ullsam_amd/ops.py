@@ -1302,6 +1302,167 @@ def split_relabel(parts_sorted: torch.Tensor, labels: torch.Tensor, d2: torch.Te
     return out, parent, peak_r2, peak_xy, parts_of, flags
 
 
+# ---- outlines of a label image: polygon loops (csrc/outline.hip; utils.outline drives these) --------------------------------------------------
+OUTLINE_FLAGS = 8          # bad id / index, E, corners, leaders, list cursor, parent chain too long, (two free)
+OUTLINE_MAX_PIXELS = 2 ** 29
+OUTLINE_CHUNK = 2048       # values per workgroup of the scan (outline.hip OL_CHUNK)
+
+
+def _outline_flags(flags: Optional[torch.Tensor], dev) -> torch.Tensor:
+    return torch.zeros((OUTLINE_FLAGS,), dtype=torch.int32, device=dev) if flags is None else _out_i32(flags, (OUTLINE_FLAGS,), dev, "flags")
+
+
+def _outline_frame(labels: torch.Tensor, what: str):
+    _chk(labels, "labels", torch.int32)
+    assert labels.dim() == 2, tuple(labels.shape)
+    h, w = labels.shape
+    if not (h >= 1 and w >= 1 and h * w < OUTLINE_MAX_PIXELS):
+        raise _lib.UllsamError(f"{what}: a frame of {h} x {w} (each side at least 1, fewer than 2^29 pixels)")
+    return h, w
+
+
+def _outline_vec(t: torch.Tensor, name: str, n: int, dtype=torch.int32):
+    _chk(t, name, dtype)
+    assert t.numel() == n, (name, tuple(t.shape), n)
+
+
+def _outline_sums(n: int, dev) -> torch.Tensor:
+    return torch.empty((max(1, -(-n // OUTLINE_CHUNK)),), dtype=torch.int32, device=dev)
+
+
+def outline_sides(labels: torch.Tensor, num: Optional[int] = None, flags: Optional[torch.Tensor] = None):
+    """labels int32 [H, W] -> (mask uint8 [H, W], off int32 [H * W], flags int32 [8]): bit s of mask = side s (top, right, bottom, left) of a labelled
+    pixel faces a pixel that is not of its label; off = the exclusive scan of popcount(mask); flags[1] = E, the edges (ullsam_hip.h outline_sides)."""
+    h, w = _outline_frame(labels, "outline_sides")
+    k = DISTANCE_INF if num is None else int(num)
+    if not 0 <= k <= DISTANCE_INF:
+        raise _lib.UllsamError(f"outline_sides: num = {num} must lie in 0..2^31 - 1")
+    dev = labels.device
+    mask = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    off = torch.empty((h * w,), dtype=torch.int32, device=dev)
+    flags = _outline_flags(flags, dev)
+    _lib.call("ullsam_outline_sides", labels.data_ptr(), h, w, k, mask.data_ptr(), off.data_ptr(), _outline_sums(h * w, dev).data_ptr(), flags.data_ptr(),
+              _stream())
+    return mask, off, flags
+
+
+def outline_scan(vals: torch.Tensor):
+    """vals uint8 [n] -> (off int32 [n] = the exclusive scan of (vals != 0), total int32 [1])."""
+    _chk(vals, "vals", torch.uint8)
+    n, dev = vals.numel(), vals.device
+    off = torch.empty((n,), dtype=torch.int32, device=dev)
+    total = torch.empty((1,), dtype=torch.int32, device=dev)
+    _lib.call("ullsam_outline_scan", _p(vals) if n else None, n, _p(off) if n else None, _outline_sums(n, dev).data_ptr(), total.data_ptr(), _stream())
+    return off, total
+
+
+def outline_successors(labels: torch.Tensor, mask: torch.Tensor, off: torch.Tensor, edges: int, connectivity: int = 8, flags: Optional[torch.Tensor] = None):
+    """outline_sides' maps and E = edges -> (eid int32 [E] = 4 * p + s in ascending order, succ int32 [E] = the compact index of every edge's successor,
+    pdir uint8 [E] = the side of every edge's predecessor, flags) (ullsam_hip.h outline_successors)."""
+    h, w = _outline_frame(labels, "outline_successors")
+    _outline_vec(mask, "mask", h * w, torch.uint8); _outline_vec(off, "off", h * w)
+    e = int(edges)
+    if connectivity not in (4, 8) or not 0 <= e <= 4 * h * w:
+        raise _lib.UllsamError(f"outline_successors: connectivity = {connectivity} must be 4 or 8 and edges = {edges} lie in 0..4 H W")
+    dev = labels.device
+    eid = torch.empty((e,), dtype=torch.int32, device=dev)
+    succ = torch.empty((e,), dtype=torch.int32, device=dev)
+    pdir = torch.empty((e,), dtype=torch.uint8, device=dev)
+    flags = _outline_flags(flags, dev)
+    _lib.call("ullsam_outline_successors", labels.data_ptr(), h, w, mask.data_ptr(), off.data_ptr(), e, int(connectivity), _p(eid) if e else None,
+              _p(succ) if e else None, _p(pdir) if e else None, flags.data_ptr(), _stream())
+    return eid, succ, pdir, flags
+
+
+def outline_rank(succ: torch.Tensor, eid: torch.Tensor, pdir: torch.Tensor, flags: Optional[torch.Tensor] = None):
+    """succ, a permutation of 0..E - 1 -> (leader int32 [E] = the smallest index of every edge's cycle, rank int32 [E] = the steps from it, flags):
+    ceil(log2 E) rounds of pointer doubling in ping-pong buffers (ullsam_hip.h outline_rank).  flags[3] += the leaders, flags[2] += the corners
+    (the edges with pdir != eid & 3)."""
+    _chk(succ, "succ", torch.int32)
+    e, dev = succ.numel(), succ.device
+    _outline_vec(eid, "eid", e); _outline_vec(pdir, "pdir", e, torch.uint8)
+    rounds = max(e - 1, 0).bit_length()
+    ws = torch.empty((2, e, 4), dtype=torch.int32, device=dev)
+    leader = torch.empty((e,), dtype=torch.int32, device=dev)
+    rank = torch.empty((e,), dtype=torch.int32, device=dev)
+    flags = _outline_flags(flags, dev)
+    _lib.call("ullsam_outline_rank", _p(succ) if e else None, _p(eid) if e else None, _p(pdir) if e else None, e, rounds, _p(ws) if e else None,
+              _p(leader) if e else None, _p(rank) if e else None, flags.data_ptr(), _stream())
+    return leader, rank, flags
+
+
+def outline_collect(labels: torch.Tensor, eid: torch.Tensor, leader: torch.Tensor, room: int, flags: Optional[torch.Tensor] = None):
+    """-> (list int64 [room], flags): label << 32 | compact index of every leader (leader[e] = e), in no particular order, from flags[4] on; the first
+    flags[4] entries are written, sorting them gives the order of the loops."""
+    _chk(labels, "labels", torch.int32); _chk(eid, "eid", torch.int32)
+    e = eid.numel()
+    _outline_vec(leader, "leader", e)
+    lst = torch.zeros((int(room),), dtype=torch.int64, device=labels.device)
+    flags = _outline_flags(flags, labels.device)
+    _lib.call("ullsam_outline_collect", labels.data_ptr(), labels.numel(), _p(eid) if e else None, _p(leader) if e else None, e,
+              _p(lst) if lst.numel() else None, lst.numel(), flags.data_ptr(), _stream())
+    return lst, flags
+
+
+def outline_loops(eid: torch.Tensor, leader: torch.Tensor, loop_of: torch.Tensor, loops: int, width: int, flags: Optional[torch.Tensor] = None):
+    """loop_of int32 [E]: at every leader, the index of its loop -> (edges int32 [L], area2 int64 [L], flags): the edge count and the shoelace sum of
+    every loop (ullsam_hip.h outline_loops)."""
+    _chk(eid, "eid", torch.int32)
+    e, n, dev = eid.numel(), int(loops), eid.device
+    _outline_vec(leader, "leader", e); _outline_vec(loop_of, "loop_of", e)
+    edges = torch.zeros((n,), dtype=torch.int32, device=dev)
+    area2 = torch.zeros((n,), dtype=torch.int64, device=dev)
+    flags = _outline_flags(flags, dev)
+    if e and n:
+        _lib.call("ullsam_outline_loops", eid.data_ptr(), leader.data_ptr(), loop_of.data_ptr(), e, n, int(width), edges.data_ptr(), area2.data_ptr(),
+                  flags.data_ptr(), _stream())
+    return edges, area2, flags
+
+
+def outline_order(eid: torch.Tensor, pdir: torch.Tensor, leader: torch.Tensor, rank: torch.Tensor, loop_of: torch.Tensor, estart: torch.Tensor,
+                  flags: Optional[torch.Tensor] = None):
+    """estart int32 [L] = the exclusive scan of the loops' edge counts -> (reid int32 [E], corner uint8 [E], flags): edge e's id and whether it is a
+    corner, at slot estart[its loop] + rank[e] -- the edges loop after loop, each loop in travel order from its leader."""
+    _chk(eid, "eid", torch.int32); _chk(estart, "estart", torch.int32)
+    e, dev = eid.numel(), eid.device
+    _outline_vec(pdir, "pdir", e, torch.uint8); _outline_vec(leader, "leader", e); _outline_vec(rank, "rank", e); _outline_vec(loop_of, "loop_of", e)
+    reid = torch.zeros((e,), dtype=torch.int32, device=dev)
+    corner = torch.zeros((e,), dtype=torch.uint8, device=dev)
+    flags = _outline_flags(flags, dev)
+    if e:
+        _lib.call("ullsam_outline_order", eid.data_ptr(), pdir.data_ptr(), leader.data_ptr(), rank.data_ptr(), loop_of.data_ptr(), _p(estart) if estart.numel() else None,
+                  e, estart.numel(), reid.data_ptr(), corner.data_ptr(), flags.data_ptr(), _stream())
+    return reid, corner, flags
+
+
+def outline_vertices(reid: torch.Tensor, corner: torch.Tensor, coff: torch.Tensor, count: int, width: int) -> torch.Tensor:
+    """vertices int32 [count, 2]: the tail (x, y) of every corner edge of outline_order's copy, at coff = outline_scan(corner)."""
+    _chk(reid, "reid", torch.int32)
+    e, n = reid.numel(), int(count)
+    _outline_vec(corner, "corner", e, torch.uint8); _outline_vec(coff, "coff", e)
+    vertices = torch.zeros((n, 2), dtype=torch.int32, device=reid.device)
+    if e and n:
+        _lib.call("ullsam_outline_vertices", reid.data_ptr(), corner.data_ptr(), coff.data_ptr(), e, int(width), n, vertices.data_ptr(), _stream())
+    return vertices
+
+
+def outline_parents(labels: torch.Tensor, mask: torch.Tensor, off: torch.Tensor, eid: torch.Tensor, leader: torch.Tensor, loop_of: torch.Tensor,
+                    lead: torch.Tensor, area2: torch.Tensor, flags: Optional[torch.Tensor] = None):
+    """lead int32 [L] = the compact index of every loop's leader, area2 int64 [L] -> (parent int32 [L], flags): an outer loop is its own parent; a hole
+    walks left from its leader's pixel and chases (ullsam_hip.h outline_parents)."""
+    h, w = _outline_frame(labels, "outline_parents")
+    _outline_vec(mask, "mask", h * w, torch.uint8); _outline_vec(off, "off", h * w)
+    _chk(eid, "eid", torch.int32); _chk(lead, "lead", torch.int32)
+    e, n, dev = eid.numel(), lead.numel(), labels.device
+    _outline_vec(leader, "leader", e); _outline_vec(loop_of, "loop_of", e); _outline_vec(area2, "area2", n, torch.int64)
+    parent = torch.empty((n,), dtype=torch.int32, device=dev)
+    flags = _outline_flags(flags, dev)
+    if n:
+        _lib.call("ullsam_outline_parents", labels.data_ptr(), h, w, mask.data_ptr(), off.data_ptr(), eid.data_ptr(), leader.data_ptr(), loop_of.data_ptr(),
+                  lead.data_ptr(), area2.data_ptr(), e, n, parent.data_ptr(), flags.data_ptr(), _stream())
+    return parent, flags
+
+
 # ---- per-instance measurements and contacts from a label image (csrc/measure.hip; utils.measure drives these) ---------------------------------
 MEASURE_MAX_SIDE = 46340  # x * x < 2^31 and H * W < 2^31: every sum of the tables stays below 2^62
 MEASURE_MAX_CHANNELS = 4
