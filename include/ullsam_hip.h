@@ -544,6 +544,36 @@ int ullsam_outline_order(const int* eid, const unsigned char* pdir, const int* l
 int ullsam_outline_vertices(const int* reid, const unsigned char* corner, const int* coff, long E, int W, long N, int* vertices, void* stream);
 int ullsam_outline_parents(const int* labels, int H, int W, const unsigned char* mask, const int* off, const int* eid, const int* leader,
                            const int* loop_of, const int* lead, const long long* area2, long E, long L, int* parent, int* flags, void* stream);
+/* Polygons to an instance label image: exact scanline rasterisation in fixed point (csrc/raster.hip; integer work, bit-exact with the host form
+   utils.raster.rasterize_polygons; definition in DESIGN.md "7b, continued (rasterising)").  q i32 [N, 2] = the vertices (x, y) in 1/256 pixel,
+   |q| <= 65535 * 256; start i32 [R + 1]: ring r owns q[start[r] : start[r + 1]], open (the last vertex joins the first); ring_label i32 [R] in
+   1..K; 1 <= H, W <= 32767, K <= 65535.  Edge i runs from vertex i to the next vertex of its ring; the centre of pixel (x, y) is (256 x + 128,
+   256 y + 128).  flags i32 [4], zeroed by the caller, only ever raised: [0] = status bits (1 = a ring_label outside 1..K, 2 = a coordinate beyond
+   the range, 4 = a total above 2^31 - 1, 8 = an index or value of a hand-made table outside its range; what is flagged is skipped, nothing is
+   indexed with it), [1] = C, the crossings.
+   raster_scan: off i32 [n] = the exclusive scan of vals i32 [n] (each in 0..32767, else it counts as 0 and bit 8), total[0] = their sum, held at
+     2^31 - 1 with bit 4 when it is larger.  sums i32 [ceil(n / 2048)] is scratch.
+   raster_edges: per edge row0 / cnt i32 [N] = the first and the number of the rows y in 0..H - 1 with min(y0, y1) <= 256 y + 128 < max(y0, y1)
+     (row0 = 0 where cnt = 0), nxt i32 [N] = the index of the edge's second vertex, elab i32 [N] = its label (0 for a flagged edge: it crosses
+     nothing); off i32 [N] = the exclusive scan of cnt, flags[1] = C.
+   raster_keys: crossing c belongs to the edge e with off[e] <= c < off[e] + cnt[e] and to row y = row0[e] + c - off[e].  With the endpoints ordered
+     by y, d = y1 - y0, cy = 256 y + 128: A = (x0 - 128) d + (cy - y0)(x1 - x0), B = 256 d, xs = clamp(ceil(A / B), 0, W): the crossing toggles the
+     pixels x >= xs of the row.  keys i64 [C][c] = label << 32 | y << 16 | xs (0 for a flagged crossing).
+   raster_covered: keys SORTED; entries 2 j, 2 j + 1 are span j = [xs_a, xs_b) of one (label, row).  covered i32 [K][k - 1] = the sum of the span
+     lengths of label k (zeroed here); len i32 [C / 2] (may be null) = the span lengths.
+   raster_paint: raw i32 [H, W] (zeroed here) = 1 + the largest rank[label - 1] (rank i32 [K], values in 0..K - 1) among the spans covering the
+     pixel.  form 0: one wave per span; form 1: one lane per pixel, poff i32 [C / 2] = raster_scan of len and total i32 [1] its sum, on the device.
+   raster_finish: label_of i32 [K + 1] = the label of every raw value (label_of[0] = 0).  labels i32 [H, W] = label_of[raw]; area i32 [K] = the
+     pixels of every label, box i32 [K, 4] = their inclusive XYXY box, (INT_MAX, INT_MAX, -1, -1) where there are none (both set here). */
+int ullsam_raster_scan(const int* vals, long n, int* off, int* sums, int* total, int* flags, void* stream);
+int ullsam_raster_edges(const int* q, long N, const int* start, long R, const int* ring_label, int H, int W, long K, int* row0, int* cnt, int* nxt,
+                        int* elab, int* off, int* sums, int* flags, void* stream);
+int ullsam_raster_keys(const int* q, long N, const int* row0, const int* cnt, const int* nxt, const int* elab, const int* off, long C, int H, int W,
+                       long K, long long* keys, int* flags, void* stream);
+int ullsam_raster_covered(const long long* keys, long C, int H, int W, long K, int* covered, int* len, int* flags, void* stream);
+int ullsam_raster_paint(const long long* keys, long C, const int* rank, int H, int W, long K, int form, const int* poff, const int* total, int* raw,
+                        int* flags, void* stream);
+int ullsam_raster_finish(const int* raw, int H, int W, const int* label_of, long K, int* labels, int* area, int* box, int* flags, void* stream);
 /* Per-instance measurements and contacts from a label image (csrc/measure.hip; integer work, bit-exact with the host forms
    utils.measure.measure_instances / label_contacts; definition in DESIGN.md "7b, continued: measurements").  labels i32 [H, W] with ids
    0..K, 0 = background, 1 <= H, W <= 46340 (x * x and every area stay below 2^31, every sum below 2^62), K <= 2^31 - 2.  Row k - 1 of every

@@ -52,7 +52,10 @@ HOT_SPLIT = [r"split_ascent_kernelILb[01]E", r"split_flatten_kernel", r"split_pa
 HOT_OUTLINE = [r"outline_sides_kernel", r"outline_sums_kernelILb[01]E", r"outline_scan_sums_kernel", r"outline_offsets_kernelILb[01]E",
                r"outline_successors_kernel", r"outline_rank_init_kernel", r"outline_rank_round_kernel", r"outline_rank_finish_kernel",
                r"outline_collect_kernel", r"outline_loops_kernel", r"outline_order_kernel", r"outline_vertices_kernel", r"outline_parents_kernel"]
-HOT_BF16 = HOT_BF16 + HOT_AMG + HOT_REGIONS + HOT_DECODE_FP8 + HOT_LABELS + HOT_MEASURE + HOT_DISTANCE + HOT_SPLIT + HOT_OUTLINE
+# polygons to a label image (csrc/raster.hip): the edges' rows, the three kernels of the int32 scan, the keys, covered, both paint forms, the finish
+HOT_RASTER = [r"raster_edges_kernel", r"raster_sums_kernel", r"raster_scan_sums_kernel", r"raster_offsets_kernel", r"raster_keys_kernel",
+              r"raster_covered_kernel", r"raster_paint_waves_kernel", r"raster_paint_pixels_kernel", r"raster_init_kernel", r"raster_finish_kernel"]
+HOT_BF16 = HOT_BF16 + HOT_AMG + HOT_REGIONS + HOT_DECODE_FP8 + HOT_LABELS + HOT_MEASURE + HOT_DISTANCE + HOT_SPLIT + HOT_OUTLINE + HOT_RASTER
 HOT = HOT_BF16
 # round 6: the persistent ring kernel (<MI0, MI1, NTW, EMODE, STAMP = false>: the six shapes without stamps): no spilled VECTOR register and no scratch.  Its tile loop keeps more scalars than the 102 SGPRs hold
 # (tile coordinates, two buffer descriptors, the kernel arguments the epilogue reads): hipcc parks the overflow in lanes of a VGPR (v_writelane / v_readlane, outside the K loop) -- counted as

@@ -1463,6 +1463,140 @@ def outline_parents(labels: torch.Tensor, mask: torch.Tensor, off: torch.Tensor,
     return parent, flags
 
 
+# ---- polygons to a label image: exact scanline rasterisation (csrc/raster.hip; utils.raster drives these) -------------------------------------
+RASTER_FLAGS = 4           # status bits (1 bad ring_label, 2 coordinate beyond the range, 4 a total above 2^31 - 1, 8 an index left its table), C, (two free)
+RASTER_MAX_SIDE = 32767
+RASTER_MAX_IDS = 65535
+RASTER_CHUNK = 2048        # values per workgroup of the scan (raster.hip RS_CHUNK)
+RASTER_FORMS = {"waves": 0, "pixels": 1}
+
+
+def _raster_flags(flags: Optional[torch.Tensor], dev) -> torch.Tensor:
+    return torch.zeros((RASTER_FLAGS,), dtype=torch.int32, device=dev) if flags is None else _out_i32(flags, (RASTER_FLAGS,), dev, "flags")
+
+
+def _raster_frame(h: int, w: int, num: int, what: str):
+    h, w, k = int(h), int(w), int(num)
+    if not (1 <= h <= RASTER_MAX_SIDE and 1 <= w <= RASTER_MAX_SIDE and 0 <= k <= RASTER_MAX_IDS):
+        raise _lib.UllsamError(f"{what}: a frame of {h} x {w} with {k} ids (each side in 1..32767, at most 65535 ids)")
+    return h, w, k
+
+
+def _raster_sums(n: int, dev) -> torch.Tensor:
+    return torch.empty((max(1, -(-n // RASTER_CHUNK)),), dtype=torch.int32, device=dev)
+
+
+def raster_scan(vals: torch.Tensor, flags: Optional[torch.Tensor] = None):
+    """vals int32 [n], each in 0..32767 -> (off int32 [n] = their exclusive scan, total int32 [1], flags); a total above 2^31 - 1 raises bit 4 of
+    flags[0] (ullsam_hip.h raster_scan)."""
+    _chk(vals, "vals", torch.int32)
+    n, dev = vals.numel(), vals.device
+    off = torch.empty((n,), dtype=torch.int32, device=dev)
+    total = torch.empty((1,), dtype=torch.int32, device=dev)
+    flags = _raster_flags(flags, dev)
+    _lib.call("ullsam_raster_scan", _p(vals) if n else None, n, _p(off) if n else None, _raster_sums(n, dev).data_ptr(), total.data_ptr(), flags.data_ptr(),
+              _stream())
+    return off, total, flags
+
+
+def raster_edges(q: torch.Tensor, start: torch.Tensor, ring_label: torch.Tensor, h: int, w: int, num: int, flags: Optional[torch.Tensor] = None):
+    """q int32 [N, 2] (1/256 pixel), start int32 [R + 1], ring_label int32 [R] -> (row0, cnt, nxt, elab, off int32 [N], flags): per edge the first and
+    the number of the rows it crosses, its second vertex, its label, and the exclusive scan of cnt; flags[1] = C (ullsam_hip.h raster_edges)."""
+    h, w, k = _raster_frame(h, w, num, "raster_edges")
+    _chk(q, "q", torch.int32); _chk(start, "start", torch.int32); _chk(ring_label, "ring_label", torch.int32)
+    assert q.dim() == 2 and q.shape[1] == 2, tuple(q.shape)
+    n, r, dev = q.shape[0], ring_label.numel(), q.device
+    assert start.numel() == r + 1 and (r >= 1 or n == 0), (tuple(start.shape), r, n)
+    row0, cnt, nxt, elab, off = (torch.empty((n,), dtype=torch.int32, device=dev) for _ in range(5))
+    flags = _raster_flags(flags, dev)
+    if n:
+        _lib.call("ullsam_raster_edges", q.data_ptr(), n, start.data_ptr(), r, ring_label.data_ptr(), h, w, k, row0.data_ptr(), cnt.data_ptr(), nxt.data_ptr(),
+                  elab.data_ptr(), off.data_ptr(), _raster_sums(n, dev).data_ptr(), flags.data_ptr(), _stream())
+    return row0, cnt, nxt, elab, off, flags
+
+
+def raster_keys(q: torch.Tensor, row0: torch.Tensor, cnt: torch.Tensor, nxt: torch.Tensor, elab: torch.Tensor, off: torch.Tensor, crossings: int, h: int,
+                w: int, num: int, flags: Optional[torch.Tensor] = None):
+    """raster_edges' tables and C = crossings -> (keys int64 [C] = label << 32 | row << 16 | xs of every crossing, in edge order, flags): one work
+    item per crossing, its edge found by a search in off (ullsam_hip.h raster_keys)."""
+    h, w, k = _raster_frame(h, w, num, "raster_keys")
+    _chk(q, "q", torch.int32)
+    n, c, dev = q.shape[0], int(crossings), q.device
+    for t, name in ((row0, "row0"), (cnt, "cnt"), (nxt, "nxt"), (elab, "elab"), (off, "off")):
+        _chk(t, name, torch.int32)
+        assert t.numel() == n, (name, tuple(t.shape), n)
+    if not 0 <= c <= DISTANCE_INF or (c and not n):
+        raise _lib.UllsamError(f"raster_keys: crossings = {crossings} must lie in 0..2^31 - 1, and 0 without an edge")
+    keys = torch.zeros((c,), dtype=torch.int64, device=dev)
+    flags = _raster_flags(flags, dev)
+    if c:
+        _lib.call("ullsam_raster_keys", q.data_ptr(), n, row0.data_ptr(), cnt.data_ptr(), nxt.data_ptr(), elab.data_ptr(), off.data_ptr(), c, h, w, k,
+                  keys.data_ptr(), flags.data_ptr(), _stream())
+    return keys, flags
+
+
+def _raster_sorted(keys: torch.Tensor, what: str) -> int:
+    _chk(keys, "keys", torch.int64)
+    if keys.numel() % 2:
+        raise _lib.UllsamError(f"{what}: {keys.numel()} keys (the crossings of closed rings come in pairs)")
+    return keys.numel()
+
+
+def raster_covered(keys: torch.Tensor, h: int, w: int, num: int, flags: Optional[torch.Tensor] = None):
+    """keys int64 [C], SORTED -> (covered int32 [K] = the pixels of the frame inside every label, before overlaps, length int32 [C / 2] = the length of
+    span j = keys[2 j], keys[2 j + 1], flags) (ullsam_hip.h raster_covered)."""
+    h, w, k = _raster_frame(h, w, num, "raster_covered")
+    c, dev = _raster_sorted(keys, "raster_covered"), keys.device
+    covered = torch.zeros((k,), dtype=torch.int32, device=dev)
+    length = torch.zeros((c // 2,), dtype=torch.int32, device=dev)
+    flags = _raster_flags(flags, dev)
+    if c and k:
+        _lib.call("ullsam_raster_covered", keys.data_ptr(), c, h, w, k, covered.data_ptr(), length.data_ptr(), flags.data_ptr(), _stream())
+    return covered, length, flags
+
+
+def raster_paint(keys: torch.Tensor, rank: torch.Tensor, h: int, w: int, form: str = "waves", length: Optional[torch.Tensor] = None,
+                 flags: Optional[torch.Tensor] = None):
+    """keys int64 [C], SORTED, rank int32 [K] (a permutation of 0..K - 1, larger = on top) -> (raw int32 [h, w] = 1 + the largest rank among the spans
+    covering the pixel, 0 where none does, flags).  form "waves": one wave per span, its lanes striding the pixels; "pixels": one lane per pixel over a
+    scan of `length` (raster_covered's), whose total stays on the device (ullsam_hip.h raster_paint)."""
+    _chk(rank, "rank", torch.int32)
+    h, w, k = _raster_frame(h, w, rank.numel(), "raster_paint")
+    c, dev = _raster_sorted(keys, "raster_paint"), keys.device
+    if form not in RASTER_FORMS:
+        raise _lib.UllsamError(f'raster_paint: form must be "waves" or "pixels", got {form!r}')
+    flags = _raster_flags(flags, dev)
+    if not (c and k):
+        return torch.zeros((h, w), dtype=torch.int32, device=dev), flags
+    poff = total = None
+    if form == "pixels":
+        if length is None:
+            raise _lib.UllsamError('raster_paint: form "pixels" needs the span lengths')
+        _chk(length, "length", torch.int32)
+        assert length.numel() == c // 2, (tuple(length.shape), c)
+        poff, total, _ = raster_scan(length, flags)
+    raw = torch.empty((h, w), dtype=torch.int32, device=dev)
+    _lib.call("ullsam_raster_paint", keys.data_ptr(), c, rank.data_ptr(), h, w, k, RASTER_FORMS[form], _p(poff), _p(total), raw.data_ptr(), flags.data_ptr(),
+              _stream())
+    return raw, flags
+
+
+def raster_finish(raw: torch.Tensor, label_of: torch.Tensor, flags: Optional[torch.Tensor] = None):
+    """raw int32 [H, W] (values 0..K), label_of int32 [K + 1] (label_of[0] = 0) -> (labels int32 [H, W] = label_of[raw], area int32 [K], box int32
+    [K, 4] inclusive XYXY, (INT_MAX, INT_MAX, -1, -1) for a label without a pixel, flags): row-major, one pass (ullsam_hip.h raster_finish)."""
+    _chk(raw, "raw", torch.int32); _chk(label_of, "label_of", torch.int32)
+    assert raw.dim() == 2 and label_of.numel() >= 1, (tuple(raw.shape), tuple(label_of.shape))
+    h, w, k = _raster_frame(raw.shape[0], raw.shape[1], label_of.numel() - 1, "raster_finish")
+    dev = raw.device
+    labels = torch.empty((h, w), dtype=torch.int32, device=dev)
+    area = torch.empty((k,), dtype=torch.int32, device=dev)
+    box = torch.empty((k, 4), dtype=torch.int32, device=dev)
+    flags = _raster_flags(flags, dev)
+    _lib.call("ullsam_raster_finish", raw.data_ptr(), h, w, label_of.data_ptr(), k, labels.data_ptr(), _p(area) if k else None, _p(box) if k else None,
+              flags.data_ptr(), _stream())
+    return labels, area, box, flags
+
+
 # ---- per-instance measurements and contacts from a label image (csrc/measure.hip; utils.measure drives these) ---------------------------------
 MEASURE_MAX_SIDE = 46340  # x * x < 2^31 and H * W < 2^31: every sum of the tables stays below 2^62
 MEASURE_MAX_CHANNELS = 4
