@@ -544,6 +544,38 @@ int ullsam_outline_order(const int* eid, const unsigned char* pdir, const int* l
 int ullsam_outline_vertices(const int* reid, const unsigned char* corner, const int* coff, long E, int W, long N, int* vertices, void* stream);
 int ullsam_outline_parents(const int* labels, int H, int W, const unsigned char* mask, const int* off, const int* eid, const int* leader,
                            const int* loop_of, const int* lead, const long long* area2, long E, long L, int* parent, int* flags, void* stream);
+/* Simplified outlines of a label image: Douglas-Peucker on label_outlines' loops with exact integer arithmetic, shared borders kept watertight
+   (csrc/simplify.hip; integer work, bit-exact with the host form utils.simplify.simplify_outlines; definition in DESIGN.md "7b, continued
+   (simplifying)").  1 <= H, W <= 32767 and H * W < 2^29.  reid i32 [E] / corner u8 [E] are outline_order's copy, estart i32 [L] the first slot
+   of every loop.  A lattice point is packed as y << 16 | x.  C candidates, L loops, L <= C.  flags i32 [4], zeroed by the caller, only ever
+   raised: [0] = an index or value of a hand-made table outside its range (skipped; nothing is indexed with it).
+   simplify_flags: cand u8 [E]: bit 0 = the tail of slot i is a candidate (a corner, or a fixed point), bit 1 = a fixed point: at least three of the
+     four pixel sides that meet there separate different values (the frame's outside is 0).
+   simplify_candidates: coff = outline_scan of cand.  cxy i32 [C] = the points, cloop i32 [C] = their loops, kept u8 [C] = fixed, nfixed i32 [L] =
+     the fixed candidates of every loop (all set here).
+   simplify_anchors: in a loop with nfixed = 0 the candidate of smallest (y, x), and the one of largest squared distance from it (ties: smallest
+     (y, x)), become kept.  ws u64 [2, L] is scratch.
+   simplify_segments: koff = outline_scan of kept, total i32 [1] its sum (on the device); cstart i32 [L + 1]: loop l owns candidates cstart[l] :
+     cstart[l + 1].  pa / pb i32 [C] = the kept candidates before / after every candidate that is not kept, cyclic in its loop (-1 for a kept
+     one).  klist i32 [C] is scratch.
+   simplify_rounds: `rounds` rounds.  In each, among the open candidates of a segment (those with the same pa) the one with the largest num against
+     the chord pa -> pb (ties: smallest (y, x)) becomes kept iff num > (T2 * den) >> 16, and the others move pa or pb to it; a segment without
+     such a candidate is closed (pa = -1).  T2 = T * T, T = the tolerance in 1/256 pixel, T <= 255 * 256.  counts i32 [rounds] (zeroed here)[r] =
+     the candidates round r kept.  ws u64 [3, C] is scratch.
+   simplify_rings: voff = outline_scan of kept, total i32 [1] = N its sum.  vertices i32 [N, 2][voff[i]] = (x, y) of every kept candidate; nvert
+     i32 [L] / area2 i64 [L] = the vertices and the shoelace sum of every loop's ring (zeroed here).  klist i32 [C] is scratch. */
+int ullsam_simplify_flags(const int* labels, int H, int W, const int* reid, const unsigned char* corner, long E, unsigned char* cand, int* flags,
+                          void* stream);
+int ullsam_simplify_candidates(const int* reid, const unsigned char* cand, const int* coff, const int* estart, long E, long L, long C, int H, int W,
+                               int* cxy, int* cloop, unsigned char* kept, int* nfixed, int* flags, void* stream);
+int ullsam_simplify_anchors(const int* cxy, const int* cloop, const int* nfixed, long C, long L, unsigned long long* ws, unsigned char* kept,
+                            int* flags, void* stream);
+int ullsam_simplify_segments(const unsigned char* kept, const int* koff, const int* total, const int* cloop, const int* cstart, long C, long L,
+                             int* klist, int* pa, int* pb, int* flags, void* stream);
+int ullsam_simplify_rounds(const int* cxy, const int* cloop, const int* cstart, long C, long L, long long T2, int rounds, unsigned long long* ws,
+                           int* pa, int* pb, unsigned char* kept, int* counts, int* flags, void* stream);
+int ullsam_simplify_rings(const int* cxy, const int* cloop, const unsigned char* kept, const int* voff, const int* total, const int* cstart, long C,
+                          long L, long N, int* klist, int* vertices, int* nvert, long long* area2, int* flags, void* stream);
 /* Polygons to an instance label image: exact scanline rasterisation in fixed point (csrc/raster.hip; integer work, bit-exact with the host form
    utils.raster.rasterize_polygons; definition in DESIGN.md "7b, continued (rasterising)").  q i32 [N, 2] = the vertices (x, y) in 1/256 pixel,
    |q| <= 65535 * 256; start i32 [R + 1]: ring r owns q[start[r] : start[r + 1]], open (the last vertex joins the first); ring_label i32 [R] in

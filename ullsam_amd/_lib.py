@@ -127,6 +127,12 @@ SIGNATURES = {
     "ullsam_outline_order": [vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp],
     "ullsam_outline_vertices": [vp, vp, vp, i64, i32, i64, vp, vp],
     "ullsam_outline_parents": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp],
+    "ullsam_simplify_flags": [vp, i32, i32, vp, vp, i64, vp, vp, vp],
+    "ullsam_simplify_candidates": [vp, vp, vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp],
+    "ullsam_simplify_anchors": [vp, vp, vp, i64, i64, vp, vp, vp, vp],
+    "ullsam_simplify_segments": [vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp],
+    "ullsam_simplify_rounds": [vp, vp, vp, i64, i64, C.c_longlong, i32, vp, vp, vp, vp, vp, vp, vp],
+    "ullsam_simplify_rings": [vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp],
     "ullsam_raster_scan": [vp, i64, vp, vp, vp, vp, vp],
     "ullsam_raster_edges": [vp, i64, vp, i64, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp],
     "ullsam_raster_keys": [vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i64, vp, vp, vp],

@@ -1463,6 +1463,139 @@ def outline_parents(labels: torch.Tensor, mask: torch.Tensor, off: torch.Tensor,
     return parent, flags
 
 
+# ---- simplified outlines: Douglas-Peucker on the loops, shared borders watertight (csrc/simplify.hip; utils.simplify drives these) ------------
+SIMPLIFY_FLAGS = 4         # an index left its table, (three free)
+SIMPLIFY_MAX_SIDE = 32767
+SIMPLIFY_MAX_T = 255 * 256
+
+
+def _simplify_flags(flags: Optional[torch.Tensor], dev) -> torch.Tensor:
+    return torch.zeros((SIMPLIFY_FLAGS,), dtype=torch.int32, device=dev) if flags is None else _out_i32(flags, (SIMPLIFY_FLAGS,), dev, "flags")
+
+
+def _simplify_frame(h: int, w: int, what: str):
+    h, w = int(h), int(w)
+    if not (1 <= h <= SIMPLIFY_MAX_SIDE and 1 <= w <= SIMPLIFY_MAX_SIDE and h * w < OUTLINE_MAX_PIXELS):
+        raise _lib.UllsamError(f"{what}: a frame of {h} x {w} (each side in 1..32767, fewer than 2^29 pixels)")
+    return h, w
+
+
+def simplify_flags(labels: torch.Tensor, reid: torch.Tensor, corner: torch.Tensor, flags: Optional[torch.Tensor] = None):
+    """labels int32 [H, W] and outline_order's copy -> (cand uint8 [E], flags): bit 0 = the tail of slot i is a candidate (a corner or a fixed point),
+    bit 1 = it is a fixed point (ullsam_hip.h simplify_flags)."""
+    _chk(labels, "labels", torch.int32); _chk(reid, "reid", torch.int32)
+    assert labels.dim() == 2, tuple(labels.shape)
+    h, w = _simplify_frame(*labels.shape, "simplify_flags")
+    e, dev = reid.numel(), labels.device
+    _outline_vec(corner, "corner", e, torch.uint8)
+    cand = torch.zeros((e,), dtype=torch.uint8, device=dev)
+    flags = _simplify_flags(flags, dev)
+    if e:
+        _lib.call("ullsam_simplify_flags", labels.data_ptr(), h, w, reid.data_ptr(), corner.data_ptr(), e, cand.data_ptr(), flags.data_ptr(), _stream())
+    return cand, flags
+
+
+def simplify_candidates(reid: torch.Tensor, cand: torch.Tensor, coff: torch.Tensor, estart: torch.Tensor, count: int, h: int, w: int,
+                        flags: Optional[torch.Tensor] = None):
+    """coff = outline_scan(cand), C = count -> (cxy int32 [C] = y << 16 | x, cloop int32 [C], kept uint8 [C] = the fixed ones, nfixed int32 [L], flags):
+    the candidates in order, loop after loop, each in travel order (ullsam_hip.h simplify_candidates)."""
+    _chk(reid, "reid", torch.int32); _chk(estart, "estart", torch.int32)
+    h, w = _simplify_frame(h, w, "simplify_candidates")
+    e, n, c, dev = reid.numel(), estart.numel(), int(count), reid.device
+    _outline_vec(cand, "cand", e, torch.uint8); _outline_vec(coff, "coff", e)
+    if not 0 <= n <= c <= e:
+        raise _lib.UllsamError(f"simplify_candidates: {n} loops, {c} candidates, {e} edges (need L <= C <= E)")
+    cxy = torch.zeros((c,), dtype=torch.int32, device=dev)
+    cloop = torch.full((c,), -1, dtype=torch.int32, device=dev)
+    kept = torch.zeros((c,), dtype=torch.uint8, device=dev)
+    nfixed = torch.zeros((n,), dtype=torch.int32, device=dev)
+    flags = _simplify_flags(flags, dev)
+    if c and n:
+        _lib.call("ullsam_simplify_candidates", reid.data_ptr(), cand.data_ptr(), coff.data_ptr(), estart.data_ptr(), e, n, c, h, w, cxy.data_ptr(),
+                  cloop.data_ptr(), kept.data_ptr(), nfixed.data_ptr(), flags.data_ptr(), _stream())
+    return cxy, cloop, kept, nfixed, flags
+
+
+def _simplify_table(cxy: torch.Tensor, cloop: torch.Tensor, kept: torch.Tensor, loops: int, what: str):
+    _chk(cxy, "cxy", torch.int32)
+    c, n = cxy.numel(), int(loops)
+    _outline_vec(cloop, "cloop", c); _outline_vec(kept, "kept", c, torch.uint8)
+    if not 0 <= n <= c:
+        raise _lib.UllsamError(f"{what}: {n} loops of {c} candidates (need L <= C)")
+    return c, n
+
+
+def simplify_anchors(cxy: torch.Tensor, cloop: torch.Tensor, nfixed: torch.Tensor, kept: torch.Tensor, flags: Optional[torch.Tensor] = None):
+    """Marks, IN kept, the two anchors of every loop without a fixed point (ullsam_hip.h simplify_anchors) -> (kept, flags)."""
+    c, n = _simplify_table(cxy, cloop, kept, nfixed.numel(), "simplify_anchors")
+    _chk(nfixed, "nfixed", torch.int32)
+    flags = _simplify_flags(flags, cxy.device)
+    if c and n:
+        ws = torch.empty((2, n), dtype=torch.int64, device=cxy.device)
+        _lib.call("ullsam_simplify_anchors", cxy.data_ptr(), cloop.data_ptr(), nfixed.data_ptr(), c, n, ws.data_ptr(), kept.data_ptr(), flags.data_ptr(), _stream())
+    return kept, flags
+
+
+def simplify_segments(kept: torch.Tensor, cloop: torch.Tensor, cstart: torch.Tensor, flags: Optional[torch.Tensor] = None):
+    """cstart int32 [L + 1] -> (pa, pb int32 [C], flags): the kept candidates before and after every candidate that is not kept, cyclic in its loop;
+    -1 for a kept one (ullsam_hip.h simplify_segments)."""
+    _chk(kept, "kept", torch.uint8); _chk(cstart, "cstart", torch.int32)
+    c, n, dev = kept.numel(), cstart.numel() - 1, kept.device
+    _outline_vec(cloop, "cloop", c)
+    if not 0 <= n <= c:
+        raise _lib.UllsamError(f"simplify_segments: {n} loops of {c} candidates (need L <= C)")
+    pa = torch.full((c,), -1, dtype=torch.int32, device=dev)
+    pb = torch.full((c,), -1, dtype=torch.int32, device=dev)
+    flags = _simplify_flags(flags, dev)
+    if c:
+        koff, total = outline_scan(kept)
+        klist = torch.empty((c,), dtype=torch.int32, device=dev)
+        _lib.call("ullsam_simplify_segments", kept.data_ptr(), koff.data_ptr(), total.data_ptr(), cloop.data_ptr(), cstart.data_ptr(), c, n, klist.data_ptr(),
+                  pa.data_ptr(), pb.data_ptr(), flags.data_ptr(), _stream())
+    return pa, pb, flags
+
+
+def simplify_rounds(cxy: torch.Tensor, cloop: torch.Tensor, cstart: torch.Tensor, t: int, rounds: int, pa: torch.Tensor, pb: torch.Tensor,
+                    kept: torch.Tensor, flags: Optional[torch.Tensor] = None):
+    """`rounds` rounds of the rule at tolerance t / 256 pixel, IN pa, pb and kept -> (counts int32 [rounds] = the candidates every round kept, flags)
+    (ullsam_hip.h simplify_rounds)."""
+    _chk(cstart, "cstart", torch.int32)
+    c, n = _simplify_table(cxy, cloop, kept, cstart.numel() - 1, "simplify_rounds")
+    _outline_vec(pa, "pa", c); _outline_vec(pb, "pb", c)
+    t, rounds = int(t), int(rounds)
+    if not (0 <= t <= SIMPLIFY_MAX_T and 1 <= rounds <= 1024):
+        raise _lib.UllsamError(f"simplify_rounds: t = {t} must lie in 0..{SIMPLIFY_MAX_T} and rounds = {rounds} in 1..1024")
+    dev = cxy.device
+    counts = torch.zeros((rounds,), dtype=torch.int32, device=dev)
+    flags = _simplify_flags(flags, dev)
+    if c:
+        ws = torch.empty((3, c), dtype=torch.int64, device=dev)
+        _lib.call("ullsam_simplify_rounds", cxy.data_ptr(), cloop.data_ptr(), cstart.data_ptr(), c, n, t * t, rounds, ws.data_ptr(), pa.data_ptr(), pb.data_ptr(),
+                  kept.data_ptr(), counts.data_ptr(), flags.data_ptr(), _stream())
+    return counts, flags
+
+
+def simplify_rings(cxy: torch.Tensor, cloop: torch.Tensor, kept: torch.Tensor, voff: torch.Tensor, total: torch.Tensor, cstart: torch.Tensor, count: int,
+                   flags: Optional[torch.Tensor] = None):
+    """voff, total = outline_scan(kept), N = count = total -> (vertices int32 [N, 2], nvert int32 [L], area2 int64 [L], flags): the kept candidates in
+    order, and the vertex count and shoelace sum of every loop's ring (ullsam_hip.h simplify_rings)."""
+    _chk(cstart, "cstart", torch.int32); _chk(total, "total", torch.int32)
+    c, n = _simplify_table(cxy, cloop, kept, cstart.numel() - 1, "simplify_rings")
+    _outline_vec(voff, "voff", c)
+    nv, dev = int(count), cxy.device
+    if not 0 <= nv <= c or total.numel() != 1:
+        raise _lib.UllsamError(f"simplify_rings: count = {count} must lie in 0..C = {c}, total hold one value")
+    vertices = torch.zeros((nv, 2), dtype=torch.int32, device=dev)
+    nvert = torch.zeros((n,), dtype=torch.int32, device=dev)
+    area2 = torch.zeros((n,), dtype=torch.int64, device=dev)
+    flags = _simplify_flags(flags, dev)
+    if c and n and nv:
+        klist = torch.empty((c,), dtype=torch.int32, device=dev)
+        _lib.call("ullsam_simplify_rings", cxy.data_ptr(), cloop.data_ptr(), kept.data_ptr(), voff.data_ptr(), total.data_ptr(), cstart.data_ptr(), c, n, nv,
+                  klist.data_ptr(), vertices.data_ptr(), nvert.data_ptr(), area2.data_ptr(), flags.data_ptr(), _stream())
+    return vertices, nvert, area2, flags
+
+
 # ---- polygons to a label image: exact scanline rasterisation (csrc/raster.hip; utils.raster drives these) -------------------------------------
 RASTER_FLAGS = 4           # status bits (1 bad ring_label, 2 coordinate beyond the range, 4 a total above 2^31 - 1, 8 an index left its table), C, (two free)
 RASTER_MAX_SIDE = 32767
