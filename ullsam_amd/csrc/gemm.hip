@@ -118,7 +118,9 @@ __device__ __forceinline__ void store_row8<bf16>(bf16* dst, const float* v, int 
 
 
 // EMODE (compile time, so the common epilogue carries none of the others' registers): 0 standard, 1 wqkv + RoPE (act 4), 2 fp8 scales
-template <typename T, typename OutT, int BM, int NTHREADS, int BN = 128, int EMODE = 0>
+// RING16: the ring kernel's LDS-staged epilogue for 2-byte outputs evaluates GELU and SwiGLU in the forms of its direct epilogues (gelu_erfc5, the hardware
+// reciprocal), so that a launch gives the same bits whichever of the two the layout selects (odd M, a row pitch or base that is not 16-byte aligned)
+template <typename T, typename OutT, int BM, int NTHREADS, int BN = 128, int EMODE = 0, bool RING16 = false>
 __device__ __forceinline__ void epilogue_rows(const GemmArgs& p, const float* Cs, int m0, int n0, int tn, int tid) {
     constexpr int TPR = BN / 8;             // threads per row (each owns 8 accumulator columns)
     constexpr int RPP = NTHREADS / TPR;     // rows per pass
@@ -139,7 +141,13 @@ __device__ __forceinline__ void epilogue_rows(const GemmArgs& p, const float* Cs
             if (gm >= p.M) continue;
             const float4 g = *reinterpret_cast<const float4*>(Cs + row * BN + grp * 128 + j0);
             const float4 u = *reinterpret_cast<const float4*>(Cs + row * BN + grp * 128 + 64 + j0);
-            float4 o = make_float4(silu_f(g.x) * u.x, silu_f(g.y) * u.y, silu_f(g.z) * u.z, silu_f(g.w) * u.w);
+            float4 o;
+            if constexpr (RING16) {
+                o = make_float4(g.x * __builtin_amdgcn_rcpf(1.0f + __expf(-g.x)) * u.x, g.y * __builtin_amdgcn_rcpf(1.0f + __expf(-g.y)) * u.y,
+                                g.z * __builtin_amdgcn_rcpf(1.0f + __expf(-g.z)) * u.z, g.w * __builtin_amdgcn_rcpf(1.0f + __expf(-g.w)) * u.w);
+            } else {
+                o = make_float4(silu_f(g.x) * u.x, silu_f(g.y) * u.y, silu_f(g.z) * u.z, silu_f(g.w) * u.w);
+            }
             OutT* dst = C + (size_t)gm * p.ldc + (size_t)tn * (BN / 2) + grp * 64 + j0;
             if (p.vec_ok) {
                 store4(dst, o);
@@ -253,7 +261,7 @@ __device__ __forceinline__ void epilogue_rows(const GemmArgs& p, const float* Cs
         for (int e = 0; e < 8; ++e) v[e] += bv[e];
         if (p.act == 1) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = gelu_erf(v[e]);
+            for (int e = 0; e < 8; ++e) v[e] = RING16 ? gelu_erfc5(v[e]) : gelu_erf(v[e]);
         } else if (p.act == 2) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
@@ -958,7 +966,7 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
         const bool odd = mm & 1;
         const int row0 = m0 + row_w + mm;
         const int rowp = row0 & ~1;   // after pair_swap the lane pair (mm, mm ^ 1) owns rows rowp + 16 i and rowp + 16 i + 1
-        const bool direct = p.vec_ok && (p.N & 7) == 0 && (p.M & 1) == 0;
+        const bool direct = p.vec_ok && (p.N & 7) == 0 && (p.M & 1) == 0 && (p.out_f32 || !p.residual);   // (the direct 2-byte epilogues add no residual)
         auto gst = [&](void* ptr, u32x4 v) __attribute__((always_inline)) { *reinterpret_cast<u32x4*>(ptr) = v; };
         if constexpr (EMODE == 1) {
             // wqkv + RoPE + KV-cache append (modeling_internlm2.py:359-388, 233-247), straight from the accumulators.  The tile's 256 columns are two
@@ -1174,7 +1182,7 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
                 }
                 __syncthreads();
                 if (p.out_f32) epilogue_rows<T, float, ROWS, NT_E, BN>(p, Cs, m0 + half * 16 * MI0, n0, tn, tid);
-                else epilogue_rows<T, T, ROWS, NT_E, BN>(p, Cs, m0 + half * 16 * MI0, n0, tn, tid);
+                else epilogue_rows<T, T, ROWS, NT_E, BN, 0, true>(p, Cs, m0 + half * 16 * MI0, n0, tn, tid);
             };
             staged(std::integral_constant<int, 0>{});
             staged(std::integral_constant<int, 1>{});
@@ -1293,7 +1301,7 @@ static bool ring_persist_ok(const GemmArgs& a) {
     if (((size_t)(a.M + BM) * a.lda + a.K) * 2 >= (1ull << 32) || ((size_t)a.N * a.ldw + a.K) * 2 >= (1ull << 32)) return false;   // 32-bit descriptor offsets
     if (EMODE == 1) return true;                                      // (the RoPE launcher has checked the alignment of q / k / v and the bias)
     if (!(a.vec_ok && (a.N & 7) == 0 && (a.M & 1) == 0)) return false;   // the direct epilogues' condition in gemm_ring8_kernel
-    if (!a.out_f32) return a.act != 3 || NTW == 4;
+    if (!a.out_f32) return !a.residual && (a.act != 3 || NTW == 4);   // (a residual on a 2-byte output: the staged epilogue of gemm_ring8_kernel)
     return a.act == 0;
 }
 template <int MI0, int MI1, int NTW, int EMODE = 0>
