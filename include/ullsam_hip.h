@@ -43,7 +43,8 @@ int ullsam_set_gemm_variant(int variant);
    key 2 = how ring launches of MORE than one round of tiles run (csrc/gemm_ring8p.h; both values give bit-equal outputs): 2 (default) = persistent grid,
    identical trips, both wave groups' epilogues together; 0 = one tile per workgroup (the kernel of rounds 2 - 5); every other value is rejected;
    key 3 = split-K on the ring kernel for launches of <= 128 tiles whose K cuts into ranges of >= 1280 that fill >= 224 workgroups: 1 (default) = where the caller allows it
-   (ullsam_gemm's act | 256), 0 = never, 2 = wherever it fits */
+   (ullsam_gemm's act | 256), 0 = never, 2 = wherever it fits;
+   key 4 = the weight as K-panels (ullsam_gemm_panels): 1 (default) = ring launches that were handed panels read them, 0 = every launch reads the row-major weight (bit-equal) */
 int ullsam_set_gemm_tuning(int key, int value);
 /* Attention kernel selection for A/B measurements and the kernel tests: 0 = production; 1 / 2 = windowed attention on the tiled kernel (7-wave /
    4-wave workgroups) instead of the whole-window kernel; 3..8 = start stagger of the whole-window kernel's second resident workgroup; 9 = global
@@ -75,6 +76,18 @@ int ullsam_gemm(int dtype, const void* A, long lda, const void* W, long ldw, voi
 int ullsam_gemm_qkv_rope(int dtype, const void* A, long lda, const void* W, long ldw, const float* bias, int B, int S, int K, int KVH,
                          int G, const int* pos, const float* cos_tab, const float* sin_tab, int tab_rows, void* q_out, void* k_cache,
                          void* v_cache, int cap, int cache_pos0, void* workspace, long ws_bytes, void* stream);
+
+/* ullsam_gemm / ullsam_gemm_qkv_rope with the bf16 weight handed over twice: row-major `W` [N, ldw] and the SAME values once more as K-panels
+ * `w_panels` = [N / 16][K / 32][16 rows][32 k] (ullsam_amd.packing.pack_ring_panels; N % 16 == 0, K % 32 == 0, 1 KiB aligned, nullable), in which one
+ * (16-row block, 32-deep k step) cell is one contiguous KiB.  The ring kernels read the panels when the launch covers whole tiles of a contiguous weight
+ * (N a multiple of the tile width, ldw == K) and ullsam_set_gemm_tuning(4, 1) holds (the default); every other kernel the dispatch picks reads `W`.
+ * The result is the same bit for bit: only the addresses the weight requests read from differ. */
+int ullsam_gemm_panels(int dtype, const void* A, long lda, const void* W, long ldw, const void* w_panels, void* C, long ldc, int out_f32,
+                       const float* bias, const float* residual, long ldr, int res_row_mod, int act, int M, int N, int K,
+                       void* workspace, long ws_bytes, void* stream);
+int ullsam_gemm_qkv_rope_panels(int dtype, const void* A, long lda, const void* W, long ldw, const void* w_panels, const float* bias, int B, int S,
+                                int K, int KVH, int G, const int* pos, const float* cos_tab, const float* sin_tab, int tab_rows, void* q_out,
+                                void* k_cache, void* v_cache, int cap, int cache_pos0, void* workspace, long ws_bytes, void* stream);
 
 /* Decode step (InternVLSAMModel.generate's token loop, modeling_internlm2.py:1112-1149; M <= 4 rows, bf16 weights): the RMSNorm that
  * precedes a layer's wqkv / w13 (modeling_internlm2.py:75-89, 598-618) folded into the GEMM that consumes it:

@@ -1,7 +1,8 @@
 """Same-process A/B of the bench step (bench.py's model, inputs and step) under GEMM dispatch variants: boxes differ by up to 12 % and
 drift with load, so only interleaved rounds in one process compare two dispatch policies.
 usage: python tools/step_ab.py [rounds] [maskA,maskB,...]     ring tile shapes the auto dispatch may pick (ullsam_set_gemm_tuning key 1):
-0 two-buffer / 128x128 kernels only, bit 0 256x256 ring, bit 1 256x320 ring, bit 2 272x256 ring (default 7)"""
+0 two-buffer / 128x128 kernels only, bit 0 256x256 ring, bit 1 256x320 ring, bit 2 272x256 ring (default 7); suffixes select the other knobs, e.g. "7w0" = the ring
+kernels read the row-major weights instead of the K-panels ("7w0,7,7w0v0": the layout A/B with an A/A pair -- the last variant is the first under another name)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -24,7 +25,11 @@ def main():
         times = {v: [] for v in variants}
         for r in range(rounds):
             for v in (variants if r % 2 == 0 else variants[::-1]):   # ABBA: the variant measured second in a round comes out ~0.5 % faster
-                head, _, pz = str(v).partition("p")     # "7p0" = dispatch mask 7 with the one-tile ring kernel (ullsam_set_gemm_tuning key 2: 0 one tile per workgroup, 2 persistent = the default)
+                head, _, wl = str(v).partition("w")     # "7w0" = dispatch mask 7 with the K-panel copies of the weights ignored (ullsam_set_gemm_tuning key 4: 0 row-major, 1 panels = the default); the suffix comes first: "7w0v0"
+                wl, _, tail = wl.partition("v")
+                lib.ullsam_set_gemm_tuning(4, int(wl) if wl else 1)
+                head = head + ("v" + tail if tail else "")
+                head, _, pz = head.partition("p")     # "7p0" = dispatch mask 7 with the one-tile ring kernel (ullsam_set_gemm_tuning key 2: 0 one tile per workgroup, 2 persistent = the default)
                 lib.ullsam_set_gemm_tuning(2, int(pz) if pz else 2)   # (2 = the library's default)
                 head, _, gm = head.partition("g")       # "7g8" = dispatch mask 7 with raster groups of 8 tile rows
                 lib.ullsam_set_gemm_tuning(0, int(gm) if gm else 4)
@@ -46,6 +51,7 @@ def main():
     lib.ullsam_set_attn_variant(0)
     lib.ullsam_set_gemm_tuning(0, 4)
     lib.ullsam_set_gemm_tuning(2, 2)
+    lib.ullsam_set_gemm_tuning(4, 1)
     for v in variants:
         t = sorted(times[v])
         print(f"dispatch mask {v}: median {t[len(t) // 2]:.3f} ms/step  (min {t[0]:.3f}, max {t[-1]:.3f})  = {4e3 / t[len(t) // 2]:.2f} images/s")

@@ -20,6 +20,8 @@ vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_long, C.c_float
 SIGNATURES = {
     "ullsam_gemm": [i32, vp, i64, vp, i64, vp, i64, i32, vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, vp],
     "ullsam_gemm_qkv_rope": [i32, vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i64, vp],
+    "ullsam_gemm_panels": [i32, vp, i64, vp, i64, vp, vp, i64, i32, vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, vp],
+    "ullsam_gemm_qkv_rope_panels": [i32, vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i64, vp],
     "ullsam_gemm_rmsnorm": [vp, i64, vp, f32, vp, i64, vp, i64, i32, vp, vp, i64, i32, i32, i32, i32, vp],
     "ullsam_decode_qkv_rope": [vp, vp, i64, vp, f32, vp, i64, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp],
     "ullsam_train_matmul": [vp, vp, vp, i32, i32, i32, i32] + [i64] * 9 + [i32, vp],

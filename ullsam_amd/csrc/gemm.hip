@@ -61,6 +61,7 @@ struct GemmArgs {
     unsigned long long* dbg;  // diagnostic launches only (ullsam_set_gemm_variant bit 15): s_memtime stamps of the ring kernel (tools/probes/ring8_stamps.py)
     // decode-step prologue (skinny kernels only): A = bf16(RMSNorm(norm_x) * norm_w), normalised while the workgroup stages its rows in LDS
     const float* norm_x; const float* norm_w; float norm_eps; long ldx;
+    const void* w_panels;   // the weight once more as K-panels (packing.pack_ring_panels), or null: read by the ring kernels where launch_ring keeps it
     int group_m;     // tile rows per raster group of the 256-row-tile kernels (tiles of a group run column-major: group_m x tiles_n); 4 by default
 };
 
@@ -788,7 +789,11 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
     // DMA pieces (16 rows x 64 B): piece q of an operand belongs to wave q % 8 (slots q / 8 = 0, 1, 2); a wave's piece count per stage
     // (na + nb, wave-uniform) is what its counted wait leaves in flight
     const char* a_base = reinterpret_cast<const char*>(p.A) + (size_t)m0 * p.lda * 2;
-    const char* b_base = reinterpret_cast<const char*>(p.W) + (size_t)n0 * p.ldw * 2;
+    // The weight as K-panels (p.w_panels, kept by launch_ring for whole tiles of a contiguous weight only; gemm_ring8p.h describes the layout): same lanes, same bytes,
+    // from whole 128-byte lines; a stage further is 1 KiB further.  BN rows of K elements are as many bytes either way, so the tile's base keeps its form.
+    const bool panels = EMODE != 2 && p.w_panels != nullptr;
+    const unsigned int kst = __builtin_amdgcn_readfirstlane(panels ? 1024u : 64u);   // bytes of W from one stage to the next
+    const char* b_base = reinterpret_cast<const char*>(panels ? p.w_panels : p.W) + (size_t)n0 * p.ldw * 2;
     const int na = (PA - wave + 7) / 8, nb = (PB - wave + 7) / 8;
     // The MFMA operands are SWAPPED (weight fragment first), so a lane's four accumulator registers of a sub-tile are four consecutive COLUMNS
     // of one output row and the epilogue can store straight from the accumulators; for 2-byte outputs the weight rows of a wave are permuted on
@@ -811,7 +816,9 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
         const int row = (wave + 8 * i) * 16 + (lane >> 2);
         const int c = (lane & 3) ^ ((row >> 2) & 2);
         a_off[i] = (unsigned int)((size_t)(min(m0 + row, p.M - 1) - m0) * p.lda * 2) + (c << 4);
-        b_off[i] = (unsigned int)((size_t)(min(n0 + w_row(row), p.N - 1) - n0) * p.ldw * 2) + (c << 4);
+        const int wr = w_row(row);
+        b_off[i] = panels ? (unsigned int)(wr >> 4) * ((unsigned int)p.K * 32u) + (unsigned int)(wr & 15) * 64u + (c << 4)
+                          : (unsigned int)((size_t)(min(n0 + wr, p.N - 1) - n0) * p.ldw * 2) + (c << 4);
     }
     const int st1 = p.K >> 5;  // stages (32-deep k-steps)
 
@@ -826,7 +833,7 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
     auto stage = [&](int s) {   // request stage s into ring slot s & 3
         char* base = smem + (s & 3) * STG;
         const char* ak = a_base + (size_t)s * 64;
-        const char* bk = b_base + (size_t)s * 64;
+        const char* bk = b_base + (size_t)s * kst;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             if (i < na) __builtin_amdgcn_global_load_lds(GLB_PTR(ak + a_off[i]), LDS_PTR(base + (wave + 8 * i) * 1024), 16, 0, 0);
@@ -887,7 +894,7 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
             {
                 char* base = smem + ((s + 2) & 3) * STG;
                 const char* ak = a_base + (size_t)(s + 2) * 64;
-                const char* bk = b_base + (size_t)(s + 2) * 64;
+                const char* bk = b_base + (size_t)(s + 2) * kst;
                 auto request = [&](int qi) __attribute__((always_inline)) {   // request qi of this wave: A0 B0 A1 B1 A2 B2 (qi is a constant after unrolling)
                     const int i = qi >> 1;
                     if (g_asm_dma) {
@@ -1250,7 +1257,7 @@ static int launch_gemm_ring_splitk(const GemmArgs& a, int S, hipStream_t stream)
     static PerDeviceOnce attr_set;
     if (attr_set.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring8_kernel<MI0, MI1, NTW, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     GemmArgs b = a;
-    b.C = a.ws; b.ldc = a.N; b.out_f32 = 1; b.bias = nullptr; b.residual = nullptr; b.act = 0; b.vec_ok = 1; b.dbg = nullptr;
+    b.C = a.ws; b.ldc = a.N; b.out_f32 = 1; b.bias = nullptr; b.residual = nullptr; b.act = 0; b.vec_ok = 1; b.dbg = nullptr; b.w_panels = nullptr;   // (a K range of panels is not a panel matrix)
     b.tiles_m = (a.M + BM - 1) / BM;
     b.tiles_n = (a.N + BN - 1) / BN;
     b.full_tiles = b.tiles_m * b.tiles_n;
@@ -1285,6 +1292,7 @@ static int ring_splitk_plan(const GemmArgs& a, int* shape) {
 // Persistent form (gemm_ring8p.h) for launches of MORE than one round of tiles whose shape and epilogue it takes; everything else -- one-round
 // launches, ragged N, K not a multiple of 128, the LDS-staged epilogues -- stays on the one-tile-per-workgroup kernel.
 static int g_persist = 2;      // ullsam_set_gemm_tuning(2, v): 0 one tile per workgroup; 2 (default) persistent ring, uniform trips, both groups' epilogues together (-0.5 % of the bench step, outputs bit-equal).  No other value: the earlier persistent forms and the ablations that 1 and 4 - 7 selected are gone
+static int g_ring_panels = 1;  // ullsam_set_gemm_tuning(4, v): 1 (default) = a ring launch that was handed the weight as K-panels reads it (launch_ring); 0 = every launch reads the row-major weight (A/B, bit-equal)
 static int cu_count() {
     static int n[32] = {};
     int d = 0;
@@ -1305,7 +1313,10 @@ static bool ring_persist_ok(const GemmArgs& a) {
     return a.act == 0;
 }
 template <int MI0, int MI1, int NTW, int EMODE = 0>
-static int launch_ring(const GemmArgs& a, hipStream_t stream) {
+static int launch_ring(const GemmArgs& a0, hipStream_t stream) {
+    // K-panels only where the layout is defined and the row-major path neither clamps nor range-checks a weight row: whole tiles of a contiguous weight
+    GemmArgs a = a0;
+    if (!(g_ring_panels && a.N % (64 * NTW) == 0 && a.K % 32 == 0 && a.ldw == a.K)) a.w_panels = nullptr;
     return ring_persist_ok<16 * (MI0 + MI1), 64 * NTW, NTW, EMODE>(a) ? launch_gemm_ring8p<MI0, MI1, NTW, EMODE>(a, stream, cu_count())
                                                                       : launch_gemm_ring8<MI0, MI1, NTW, EMODE>(a, stream);
 }
@@ -1465,7 +1476,7 @@ extern "C" int ullsam_gemm_fp8(const void* A8, long lda, const float* a_scale, c
     a.group_m = 4;   // gemm256f8_kernel rasters with a fixed group height
     a.vec_ok = vec ? 1 : 0;
     a.ws = nullptr; a.ws_bytes = 0; a.ksplit = 1;
-    a.row_scale = a_scale; a.col_scale = w_scale; a.dbg = nullptr;
+    a.row_scale = a_scale; a.col_scale = w_scale; a.dbg = nullptr; a.w_panels = nullptr;
     a.tiles_m = (M + 255) / 256; a.tiles_n = (N + 255) / 256; a.full_tiles = a.tiles_m * a.tiles_n;
     static PerDeviceOnce attr_set;
     if (attr_set.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256f8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
@@ -1480,6 +1491,7 @@ extern "C" int ullsam_set_gemm_tuning(int key, int value) {
     if (key == 1 && value >= 0 && value <= 7) { g_auto_mask = value; return 0; }
     if (key == 2 && (value == 0 || value == 2)) { g_persist = value; return 0; }
     if (key == 3 && value >= 0 && value <= 2) { g_ring_splitk = value; return 0; }
+    if (key == 4 && (value == 0 || value == 1)) { g_ring_panels = value; return 0; }
     ullsam_set_error("ullsam_set_gemm_tuning: unknown key %d / bad value %d", key, value);
     return -1;
 }
@@ -2091,7 +2103,7 @@ struct NormPrologue { const float* x; long ldx; const float* w; float eps; };
 
 static int gemm_impl(int dtype, const void* A, long lda, const void* W, long ldw, void* C, long ldc, int out_f32,
                      const float* bias, const float* residual, long ldr, int res_row_mod, int act, int M, int N,
-                     int K, void* workspace, long ws_bytes, void* stream, const RopeEpilogue* rope, const NormPrologue* norm = nullptr) {
+                     int K, void* workspace, long ws_bytes, void* stream, const RopeEpilogue* rope, const NormPrologue* norm = nullptr, const void* w_panels = nullptr) {
     ULLSAM_CHECK(dtype == ULLSAM_DT_F32 || dtype == ULLSAM_DT_BF16, "ullsam_gemm: bad dtype %d", dtype);
     ULLSAM_CHECK(M > 0 && N > 0 && K > 0, "ullsam_gemm: empty problem M=%d N=%d K=%d", M, N, K);
     const int esz = dtype == ULLSAM_DT_F32 ? 4 : 2;
@@ -2116,7 +2128,9 @@ static int gemm_impl(int dtype, const void* A, long lda, const void* W, long ldw
                      "ullsam_gemm: the RMSNorm prologue needs 16-byte aligned fp32 rows and weight");
         a.norm_x = norm->x; a.norm_w = norm->w; a.norm_eps = norm->eps; a.ldx = norm->ldx;
     }
-    a.A = A; a.W = W; a.C = C; a.bias = bias; a.residual = residual;
+    ULLSAM_CHECK(!w_panels || (dtype == ULLSAM_DT_BF16 && ((uintptr_t)w_panels & 1023) == 0 && N % 16 == 0 && K % 32 == 0),
+                 "ullsam_gemm: K-panels are bf16 [N / 16][K / 32][16][32], 1 KiB aligned (N=%d K=%d)", N, K);
+    a.A = A; a.W = W; a.C = C; a.bias = bias; a.residual = residual; a.w_panels = w_panels;
     a.M = M; a.N = N; a.K = K;
     a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr;
     a.res_row_mod = res_row_mod; a.act = act; a.out_f32 = out_f32;
@@ -2197,6 +2211,15 @@ extern "C" int ullsam_gemm(int dtype, const void* A, long lda, const void* W, lo
                            int K, void* workspace, long ws_bytes, void* stream) {
     ULLSAM_CHECK(act != 4, "ullsam_gemm: act 4 is ullsam_gemm_qkv_rope");
     return gemm_impl(dtype, A, lda, W, ldw, C, ldc, out_f32, bias, residual, ldr, res_row_mod, act, M, N, K, workspace, ws_bytes, stream, nullptr);
+}
+
+// ullsam_gemm with the weight handed over twice: row-major `W` and the same bytes as K-panels `w_panels` (packing.pack_ring_panels).  The ring kernels
+// read the panels where launch_ring allows it; every other kernel the dispatch picks reads `W`.  Same result, bit for bit.
+extern "C" int ullsam_gemm_panels(int dtype, const void* A, long lda, const void* W, long ldw, const void* w_panels, void* C, long ldc, int out_f32,
+                                  const float* bias, const float* residual, long ldr, int res_row_mod, int act, int M, int N,
+                                  int K, void* workspace, long ws_bytes, void* stream) {
+    ULLSAM_CHECK(act != 4, "ullsam_gemm_panels: act 4 is ullsam_gemm_qkv_rope_panels");
+    return gemm_impl(dtype, A, lda, W, ldw, C, ldc, out_f32, bias, residual, ldr, res_row_mod, act, M, N, K, workspace, ws_bytes, stream, nullptr, nullptr, w_panels);
 }
 
 // Decode step: out = act(bf16(RMSNorm(x) * norm_w) @ W^T + bias) (+ residual) for M <= 4 rows of K <= 4096 fp32 elements -- the norm that precedes
@@ -2291,4 +2314,15 @@ extern "C" int ullsam_gemm_qkv_rope(int dtype, const void* A, long lda, const vo
     RopeEpilogue r{pos, cos_tab, sin_tab, q_out, k_cache, v_cache, S, KVH, G, cap, cache_pos0, tab_rows};
     const int N = KVH * (G + 2) * 128;
     return gemm_impl(dtype, A, lda, W, ldw, q_out, (long)KVH * G * 128, 0, bias, nullptr, 0, 0, 4, B * S, N, K, workspace, ws_bytes, stream, &r);
+}
+// ... with the weight as K-panels as well (ullsam_gemm_panels)
+extern "C" int ullsam_gemm_qkv_rope_panels(int dtype, const void* A, long lda, const void* W, long ldw, const void* w_panels, const float* bias, int B, int S,
+                                           int K, int KVH, int G, const int* pos, const float* cos_tab, const float* sin_tab, int tab_rows, void* q_out,
+                                           void* k_cache, void* v_cache, int cap, int cache_pos0, void* workspace, long ws_bytes, void* stream) {
+    ULLSAM_CHECK(B > 0 && S > 0 && KVH > 0 && G > 0 && tab_rows > 0, "ullsam_gemm_qkv_rope_panels: bad dims");
+    ULLSAM_CHECK(cache_pos0 + S <= cap, "ullsam_gemm_qkv_rope_panels: cache overflow (%d + %d > %d)", cache_pos0, S, cap);
+    ULLSAM_CHECK(((uintptr_t)q_out & 15) == 0 && ((uintptr_t)k_cache & 15) == 0 && ((uintptr_t)v_cache & 15) == 0, "ullsam_gemm_qkv_rope_panels: 16-byte aligned outputs needed");
+    RopeEpilogue r{pos, cos_tab, sin_tab, q_out, k_cache, v_cache, S, KVH, G, cap, cache_pos0, tab_rows};
+    const int N = KVH * (G + 2) * 128;
+    return gemm_impl(dtype, A, lda, W, ldw, q_out, (long)KVH * G * 128, 0, bias, nullptr, 0, 0, 4, B * S, N, K, workspace, ws_bytes, stream, &r, nullptr, w_panels);
 }

@@ -116,6 +116,14 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
     // per-lane source offsets inside a tile (the same in every tile: rows past M are out of the descriptor's range, N % BN == 0).  They -- and the LDS read
     // bases below -- are RECOMPUTED from an opaque copy of the lane id at the start of every tile (a few dozen VALU instructions per tile) instead of living
     // across the epilogue, whose registers they would otherwise take: the 256x320 instantiation spilled 80 registers with them live.
+    // The weight as K-panels (p.w_panels, packing.pack_ring_panels: [N / 16][K / 32][16 rows][32 k], one (16-row block, stage) cell = one aligned KiB): weight row R'
+    // of the tile sits at (R' / 16) (K / 32) 1024 + (R' % 16) 64, a stage further is 1024 bytes further -- a request reads whole 128-byte lines (four 256-byte runs under
+    // the epilogues' row permutations, which keep four consecutive rows together) where the row-major weight gives it sixteen half lines in sixteen rows.  Same lanes,
+    // same bytes, same LDS image; the tile step b_tile keeps its value (BN rows of K elements either way).
+    const bool panels = p.w_panels != nullptr;
+    const int wp_shift = panels ? 4 : 0;
+    const unsigned int wp_mask = panels ? 15u : 0u, wp_block = panels ? (unsigned int)p.K * 32u : (unsigned int)(p.ldw * 2);
+    const unsigned int kst = __builtin_amdgcn_readfirstlane(panels ? 1024u : 64u);   // bytes of W from one stage to the next
     unsigned int a_off[3], b_off[3];
     auto set_offsets = [&](int ln) __attribute__((always_inline)) {
 #pragma unroll
@@ -123,12 +131,13 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
             const int row = (wave + 8 * i) * 16 + (ln >> 2);
             const int c = (ln & 3) ^ ((row >> 2) & 2);
             a_off[i] = (unsigned int)row * (unsigned int)(p.lda * 2) + (c << 4);
-            b_off[i] = (unsigned int)w_row(row) * (unsigned int)(p.ldw * 2) + (c << 4);
+            const unsigned int wr = (unsigned int)w_row(row);
+            b_off[i] = (wr >> wp_shift) * wp_block + (wr & wp_mask) * 64u + (c << 4);
         }
     };
     set_offsets(lane);
     const u32x4 a_desc = raw_desc(p.A, (unsigned int)(((size_t)(p.M - 1) * p.lda + p.K) * 2));
-    const u32x4 b_desc = raw_desc(p.W, (unsigned int)(((size_t)(p.N - 1) * p.ldw + p.K) * 2));
+    const u32x4 b_desc = raw_desc(panels ? p.w_panels : p.W, (unsigned int)(((size_t)(p.N - 1) * p.ldw + p.K) * 2));
     const unsigned int a_tile = (unsigned int)(p.lda * 2) * BM, b_tile = (unsigned int)(p.ldw * 2) * BN;   // bytes from one tile row / column to the next
     const int st1 = p.K >> 5;  // stages (32-deep k-steps) per tile, a multiple of 4, at least 12
     const unsigned int wbase = __builtin_amdgcn_readfirstlane((unsigned int)(uintptr_t)LDS_PTR(smem + wave * 1024));   // LDS address of this wave's first piece in ring slot 0
@@ -159,7 +168,7 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
     tile_of(blockIdx.x, tm0, tn0);
     bias_dma(tn0 * BN, 0);
     request_stage(tm0 * a_tile, tn0 * b_tile, 0);
-    request_stage(tm0 * a_tile + 64, tn0 * b_tile + 64, 1);
+    request_stage(tm0 * a_tile + 64, tn0 * b_tile + kst, 1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (grp == 1) __builtin_amdgcn_s_barrier();
@@ -168,6 +177,7 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
     auto core = [&](auto MIW_c, auto ROWW_c) __attribute__((always_inline)) {
         constexpr int MIW = decltype(MIW_c)::value;
         constexpr int DG = 2;   // request distance: stages between a request and its use (the one-tile kernel's)
+        const unsigned int kstep[4] = {kst * DG, kst * (DG + 1), kst * (DG + 2), kst * (DG + 3)};   // W's byte offset of the stage requested from ring slot J, relative to the trip's scalar offset
         const int row_w = decltype(ROWW_c)::value >= 0 ? decltype(ROWW_c)::value : wm * (MI0 * 16);   // first tile row of this wave's row (run time when both rows share one instantiation)
         f32x4 acc[MIW][NTW];
 #pragma unroll
@@ -195,7 +205,7 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
             constexpr int J = decltype(J_c)::value;
             constexpr int NA = decltype(NA_c)::value, NB = decltype(NB_c)::value;
             constexpr int RS = (J + DG) & 3, KOFF = 64 * (J + DG);
-            const unsigned int rq_a = so_a + KOFF, rq_b = so_b + KOFF;   // (two scalar adds per stage)
+            const unsigned int rq_a = so_a + KOFF, rq_b = so_b + kstep[J];   // (two scalar adds per stage; W's step is a scalar: 64 bytes row-major, 1024 as panels)
             // this stage's read bases: the wave's per-lane bases (rd_a / rd_b, below) + the slot's offset, ONE add each, pinned here -- left to itself
             // hipcc keeps a base register per slot and (where it cannot see that the swizzle depends on the lane only) per fragment: 20 registers and
             // spills in the 256x320 instantiation; the fragments then sit at immediate offsets of 1 KiB
@@ -254,15 +264,16 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
         auto run_tile = [&](auto NA_c, auto NB_c, unsigned int sa, unsigned int sb, unsigned int san, unsigned int sbn) __attribute__((always_inline)) {
             using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
             const int ntrip = st1 >> 2;
+            const unsigned int ktrip = 4u * kst;
             unsigned int ra = sa, rb = sb;
             for (int t = 0; t < ntrip; ++t) {
                 const bool last = t == ntrip - 1;   // (no stamps inside a stage: inside the one loop body they cost the loop its shape -- 3 x the cycles per stage; the tile-level stamps stay)
-                const unsigned int ha = last ? san - 256u : ra, hb = last ? sbn - 256u : rb;   // stages 2 / 3 of the last trip request stages 0 / 1 of the next tile: (san - 256) + 64 (J + 2)
+                const unsigned int ha = last ? san - 256u : ra, hb = last ? sbn - ktrip : rb;   // stages 2 / 3 of the last trip request stages 0 / 1 of the next tile: (san - 256) + 64 (J + 2)
                 stage(I0{}, ra, rb, NA_c, NB_c);
                 stage(I1{}, ra, rb, NA_c, NB_c);
                 stage(I2{}, ha, hb, NA_c, NB_c);
                 stage(I3{}, ha, hb, NA_c, NB_c);
-                ra += 256; rb += 256;
+                ra += 256; rb += ktrip;
             }
         };
 

@@ -11,6 +11,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..packing import pack_ring_panels
 
 
 class PackCache:
@@ -54,6 +55,15 @@ class Packed(nn.Module):
         return self.pk(name + ":cdt", p, lambda: p.detach().to(dtype).contiguous())
 
 
+def ring_panels(owner: "Packed", name: str, srcs, M: int, dtype, rows: Callable[[], torch.Tensor]) -> Optional[torch.Tensor]:
+    """The K-panel copy of the [N, K] weight `rows()` (cached in `owner` under `name`, keyed by the version of `srcs`) for a launch of M rows, or None."""
+    ps = (srcs,) if isinstance(srcs, torch.Tensor) else srcs
+    N, K = (sum(p.shape[0] for p in ps), ps[0].shape[1])
+    if not ops.ring_panels_wanted(M, N, K, dtype) or (torch.is_grad_enabled() and any(p.requires_grad for p in ps)):
+        return None
+    return owner.pk(f"{name}:panels:{dtype}", srcs, lambda: pack_ring_panels(rows()))
+
+
 class Linear(Packed):
     """Parameter holder with nn.Linear's state_dict layout (weight [out, in], bias [out])."""
 
@@ -71,6 +81,11 @@ class Linear(Packed):
 
     def b(self):
         return None if self.bias is None else self.f32("b", self.bias)
+
+    def wp(self, dtype, M: int):
+        """w(dtype) once more as the ring GEMM's K-panels (packing.pack_ring_panels) for a launch of M rows, or None: built on the first launch that
+        can read it (ops.ring_panels_wanted), once per weight version, and never while the weight is being trained (it changes every step)."""
+        return ring_panels(self, "w", self.weight, M, dtype, lambda: self.w(dtype))
 
     def w8(self):
         """(e4m3 bytes [out, in], fp32 per-output-channel scales [out]) for the fp8 GEMM; quantised once per weight version."""
@@ -93,7 +108,7 @@ class Linear(Packed):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         dt = self.weight.dtype
-        y = ops.gemm(ops.cast(x.reshape(-1, self.in_features).contiguous(), dt), self.w(dt), self.b())
+        y = ops.gemm(ops.cast(x.reshape(-1, self.in_features).contiguous(), dt), self.w(dt), self.b(), w_panels=self.wp(dt, x.numel() // self.in_features))
         return y.reshape(*x.shape[:-1], self.out_features)
 
 
@@ -145,6 +160,6 @@ class MLPBlock(Packed):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         dt = self.lin1.weight.dtype
-        h = ops.gemm(ops.cast(x.reshape(-1, x.shape[-1]).contiguous(), dt), self.lin1.w(dt), self.lin1.b(), act=self.act_code)
-        y = ops.gemm(h, self.lin2.w(dt), self.lin2.b())
+        h = ops.gemm(ops.cast(x.reshape(-1, x.shape[-1]).contiguous(), dt), self.lin1.w(dt), self.lin1.b(), act=self.act_code, w_panels=self.lin1.wp(dt, x.numel() // x.shape[-1]))
+        y = ops.gemm(h, self.lin2.w(dt), self.lin2.b(), w_panels=self.lin2.wp(dt, h.shape[0]))
         return y.reshape(x.shape)

@@ -155,19 +155,19 @@ class ImageEncoderViT(Packed):
                 qkv = ops.gemm_fp8(q8, sa, *at.qkv.w8(), at.qkv.b())
             else:
                 xn = ops.norm(xres, *blk.norm1.wb(), blk.norm1.eps, dt)
-                qkv = ops.gemm(xn, at.qkv.w(dt), at.qkv.b())
+                qkv = ops.gemm(xn, at.qkv.w(dt), at.qkv.b(), w_panels=at.qkv.wp(dt, xn.shape[0]))
             qb = at.qkv.bias if at.qkv.bias is not None else torch.zeros(3 * D, device=x.device)
             n_rel = blk.window_size if blk.window_size > 0 else g
             att = ops.vit_attention(qkv, at.rel_table("rh", at.rel_pos_h, n_rel, dt), at.rel_table("rw", at.rel_pos_w, n_rel, dt), at.cdt("qb", qb, dt),
                                     B, self.num_heads, at.head_dim, g, g, blk.window_size)
-            ops.gemm(att, at.proj.w(dt), at.proj.b(), residual=xres, out_f32=True, out=xres)
+            ops.gemm(att, at.proj.w(dt), at.proj.b(), residual=xres, out_f32=True, out=xres, w_panels=at.proj.wp(dt, att.shape[0]))
             if fp8:
                 q8, sa = ops.rows_fp8(xres, *blk.norm2.wb(), blk.norm2.eps)
                 h = ops.gemm_fp8(q8, sa, *blk.mlp.lin1.w8(), blk.mlp.lin1.b(), act=blk.mlp.act_code)
             else:
                 xn = ops.norm(xres, *blk.norm2.wb(), blk.norm2.eps, dt)
-                h = ops.gemm(xn, blk.mlp.lin1.w(dt), blk.mlp.lin1.b(), act=blk.mlp.act_code)
-            ops.gemm(h, blk.mlp.lin2.w(dt), blk.mlp.lin2.b(), residual=xres, out_f32=True, out=xres)
+                h = ops.gemm(xn, blk.mlp.lin1.w(dt), blk.mlp.lin1.b(), act=blk.mlp.act_code, w_panels=blk.mlp.lin1.wp(dt, xn.shape[0]))
+            ops.gemm(h, blk.mlp.lin2.w(dt), blk.mlp.lin2.b(), residual=xres, out_f32=True, out=xres, w_panels=blk.mlp.lin2.wp(dt, h.shape[0]))
             if self.stage_probe is not None:
                 self.stage_probe(bi, xres)
         n0, n1, n2, n3 = self.neck[0], self.neck[1], self.neck[2], self.neck[3]

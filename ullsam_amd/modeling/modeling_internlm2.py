@@ -21,7 +21,7 @@ from torch import nn
 from .. import ops
 from ..packing import pack_w13
 from ..sampling import row_seeds
-from .common import Linear, Packed
+from .common import Linear, Packed, ring_panels
 from .configuration_internlm2 import InternLM2Config
 from .outputs import BaseModelOutputWithPast, CausalLMOutputWithPast
 
@@ -52,6 +52,10 @@ class InternLM2MLP(Packed):
 
     def w13(self, dt):
         return self.pk("w13", (self.w1.weight, self.w3.weight), lambda: pack_w13(self.w1.weight.detach().to(dt), self.w3.weight.detach().to(dt)))
+
+    def w13p(self, dt, M: int):
+        """w13(dt) once more as the ring GEMM's K-panels for a launch of M rows, or None (common.ring_panels)."""
+        return ring_panels(self, "w13", (self.w1.weight, self.w3.weight), M, dt, lambda: self.w13(dt))
 
     def w13_w8d(self, dt):
         """e4m3 bytes + per-row scales of the PACKED [gate | up] rows (quantised after packing: the rows the kernel reads are the rows that were scaled)."""
@@ -211,9 +215,9 @@ class InternLM2Model(Packed):
             else:
                 xn = ops.norm(x, layer.attention_norm.w(), None, layer.attention_norm.variance_epsilon, dt, rms=True)
                 if hd == 128 and S > 8:   # prefill: head split + RoPE + KV append in the wqkv GEMM's epilogue (no qkv round trip)
-                    q = ops.gemm_qkv_rope(xn, at.wqkv.w(dt), at.wqkv.b(), kc, vc, pos, cos, sin, B, S, KVH, G, past)
+                    q = ops.gemm_qkv_rope(xn, at.wqkv.w(dt), at.wqkv.b(), kc, vc, pos, cos, sin, B, S, KVH, G, past, w_panels=at.wqkv.wp(dt, B * S))
                 else:
-                    qkv = ops.gemm(xn, at.wqkv.w(dt), at.wqkv.b())
+                    qkv = ops.gemm(xn, at.wqkv.w(dt), at.wqkv.b(), w_panels=at.wqkv.wp(dt, B * S))
                     q = ops.rope_split(qkv, kc, vc, pos, cos, sin, B, S, KVH, G, hd, past)
             if S > 1:
                 a = ops.causal_attention(q, kc, vc, key_mask, B, H, KVH, hd, S, Sk, past)
@@ -226,18 +230,18 @@ class InternLM2Model(Packed):
             if w8_wo:
                 ops.gemm_w8(a, *at.wo.w8d(), at.wo.b(), residual=x, out_f32=True, out=x)
             else:
-                ops.gemm(a, at.wo.w(dt), at.wo.b(), residual=x, out_f32=True, out=x)
+                ops.gemm(a, at.wo.w(dt), at.wo.b(), residual=x, out_f32=True, out=x, w_panels=at.wo.wp(dt, B * S))
             if w8:
                 hmid = ops.gemm_w8(x, *ff.w13_w8d(dt), act=ops.ACT_SWIGLU, norm_w=layer.ffn_norm.w(), eps=layer.ffn_norm.variance_epsilon)
             elif fused:
                 hmid = ops.gemm_rmsnorm(x, layer.ffn_norm.w(), layer.ffn_norm.variance_epsilon, ff.w13(dt), act=ops.ACT_SWIGLU)
             else:
                 xn = ops.norm(x, layer.ffn_norm.w(), None, layer.ffn_norm.variance_epsilon, dt, rms=True)
-                hmid = ops.gemm(xn, ff.w13(dt), act=ops.ACT_SWIGLU)
+                hmid = ops.gemm(xn, ff.w13(dt), act=ops.ACT_SWIGLU, w_panels=ff.w13p(dt, B * S))
             if w8_w2:
                 ops.gemm_w8(hmid, *ff.w2.w8d(), None, residual=x, out_f32=True, out=x)
             else:
-                ops.gemm(hmid, ff.w2.w(dt), None, residual=x, out_f32=True, out=x)
+                ops.gemm(hmid, ff.w2.w(dt), None, residual=x, out_f32=True, out=x, w_panels=ff.w2.wp(dt, B * S))
             if self.stage_probe is not None:
                 self.stage_probe(li, x)
         if cache is not None:

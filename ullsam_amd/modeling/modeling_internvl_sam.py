@@ -81,16 +81,16 @@ class InternVLSAMModel(Packed):
         dt = self.dtype
         ln, l1, l3 = self.mlp1[0], self.mlp1[1], self.mlp1[3]
         f = ops.pixel_shuffle_ln(img_tok, *ln.wb(), B, 64, 64, 256, ln.eps, dt)
-        h = ops.gemm(f, l1.w(dt), l1.b(), act=ops.ACT_GELU)
-        return ops.gemm(h, l3.w(dt), l3.b(), out_f32=True)
+        h = ops.gemm(f, l1.w(dt), l1.b(), act=ops.ACT_GELU, w_panels=l1.wp(dt, f.shape[0]))
+        return ops.gemm(h, l3.w(dt), l3.b(), out_f32=True, w_panels=l3.wp(dt, h.shape[0]))
 
     def _mlp2_tokens(self, rows: torch.Tensor, B: int) -> torch.Tensor:
         """mlp2 + inverse pixel shuffle (:253-270): hidden rows [B*1024, Dl] (model dtype) -> dense feature tokens fp32 [B,4096,256]."""
         dt = self.dtype
         ln, l1, l3 = self.mlp2[0], self.mlp2[1], self.mlp2[3]
         f = ops.norm(rows, *ln.wb(), ln.eps, dt)
-        f = ops.gemm(f, l1.w(dt), l1.b(), act=ops.ACT_GELU)
-        f = ops.gemm(f, l3.w(dt), l3.b(), out_f32=True)
+        f = ops.gemm(f, l1.w(dt), l1.b(), act=ops.ACT_GELU, w_panels=l1.wp(dt, f.shape[0]))
+        f = ops.gemm(f, l3.w(dt), l3.b(), out_f32=True, w_panels=l3.wp(dt, f.shape[0]))
         return ops.pixel_unshuffle(f, B, 64, 64, 256)
 
     # -- reference API ------------------------------------------------------------------------------------------------

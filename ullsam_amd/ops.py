@@ -5,6 +5,7 @@ HIP kernels from libullsam_hip.so; none falls back to torch math.
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import numpy as np
@@ -48,6 +49,24 @@ def _chk(t: torch.Tensor, name: str, dtype=None):
 
 _WS = {}
 
+# The ring GEMM's weights once more as K-panels (packing.pack_ring_panels, csrc/gemm_ring8p.h): one more bf16 copy of every weight whose launches reach a
+# ring kernel (DESIGN.md section 3 has the memory bill).  ULLSAM_RING_PANELS=0 in the environment -- or set_ring_panels(False) -- is the off switch: no copy is
+# built and every launch reads the row-major weight.  Same results either way, bit for bit.
+_RING_PANELS = os.environ.get("ULLSAM_RING_PANELS", "1") != "0"
+
+
+def set_ring_panels(on: bool) -> None:
+    """Process-wide: build and use K-panel copies of the ring GEMM's weights (default), or not.  Copies already built stay in their owners' caches."""
+    global _RING_PANELS
+    _RING_PANELS = bool(on)
+    _lib.call("ullsam_set_gemm_tuning", 4, 1 if on else 0)
+
+
+def ring_panels_wanted(M: int, N: int, K: int, dtype: torch.dtype) -> bool:
+    """Whether a launch of this shape reads K-panels if it is handed them: the shapes the dispatch of csrc/gemm.hip gives to a ring kernel on whole tiles
+    (bf16, >= 1024 rows, N a multiple of a tile width).  A copy built for a launch that ends on another kernel costs memory only -- that kernel reads `w`."""
+    return _RING_PANELS and dtype == torch.bfloat16 and M >= 1024 and K >= 256 and K % 64 == 0 and (N % 256 == 0 or N % 320 == 0)
+
 
 def _gemm_workspace(device) -> torch.Tensor:
     """Caller-owned scratch for the GEMM's split-K forms (one 128 MiB buffer per device AND stream: launches on different
@@ -60,8 +79,10 @@ def _gemm_workspace(device) -> torch.Tensor:
 
 
 def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
-         act: int = ACT_NONE, out_f32: bool = False, out: Optional[torch.Tensor] = None, res_row_mod: int = 0, splitk_ok: bool = False) -> torch.Tensor:
-    """out[M, N'] = act(a[M,K] @ w[N,K]^T + bias) + residual   (N' = N/2 for ACT_SWIGLU).  splitk_ok: a launch of few tiles under a long K may run as K ranges
+         act: int = ACT_NONE, out_f32: bool = False, out: Optional[torch.Tensor] = None, res_row_mod: int = 0, splitk_ok: bool = False,
+         w_panels: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[M, N'] = act(a[M,K] @ w[N,K]^T + bias) + residual   (N' = N/2 for ACT_SWIGLU).  w_panels: `w` once more as packing.pack_ring_panels lays it
+    out (bf16) -- the ring kernels read it instead of `w` where they can, every other kernel reads `w`; same bits either way.  splitk_ok: a launch of few tiles under a long K may run as K ranges
     summed apart (ULLSAM_ACT_SPLITK_OK, include/ullsam_hip.h): not bit-equal to the one-launch kernels -- the training step's frozen linears only."""
     _chk(a, "a"); _chk(w, "w", a.dtype)
     M, K = a.shape
@@ -81,6 +102,12 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
         _chk(residual, "residual", torch.float32)
         ldr = residual.shape[-1]
     ws = _gemm_workspace(a.device)
+    if w_panels is not None:
+        _chk(w_panels, "w_panels", torch.bfloat16)
+        assert w_panels.shape == w.shape and a.dtype == torch.bfloat16, (w_panels.shape, w.shape, a.dtype)
+        _lib.call("ullsam_gemm_panels", dt_code(a.dtype), a.data_ptr(), K, w.data_ptr(), K, w_panels.data_ptr(), out.data_ptr(), n_out, int(out_f32),
+                  _p(bias), _p(residual), ldr, res_row_mod, act | (ACT_SPLITK_OK if splitk_ok else 0), M, N, K, ws.data_ptr(), ws.numel(), _stream())
+        return out
     _lib.call("ullsam_gemm", dt_code(a.dtype), a.data_ptr(), K, w.data_ptr(), K, out.data_ptr(), n_out, int(out_f32),
               _p(bias), _p(residual), ldr, res_row_mod, act | (ACT_SPLITK_OK if splitk_ok else 0), M, N, K, ws.data_ptr(), ws.numel(), _stream())
     return out
@@ -469,7 +496,7 @@ def rope_split(qkv, k_cache, v_cache, pos, cos_tab, sin_tab, B, S, KVH, G, hd, c
 
 
 def gemm_qkv_rope(x: torch.Tensor, wqkv: torch.Tensor, bias: Optional[torch.Tensor], k_cache, v_cache, pos, cos_tab, sin_tab, B, S, KVH, G,
-                  cache_pos0) -> torch.Tensor:
+                  cache_pos0, w_panels: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q = rope(split(x @ wqkv^T + bias)) with k (rotated) / v appended to the caches, all in the GEMM's epilogue (head_dim 128)."""
     _chk(x, "x"); _chk(wqkv, "wqkv", x.dtype); _chk(pos, "position_ids", torch.int32); _chk(cos_tab, "cos", torch.float32); _chk(sin_tab, "sin", torch.float32)
     _chk(k_cache, "k_cache", x.dtype); _chk(v_cache, "v_cache", x.dtype)
@@ -479,6 +506,13 @@ def gemm_qkv_rope(x: torch.Tensor, wqkv: torch.Tensor, bias: Optional[torch.Tens
         _chk(bias, "bias", torch.float32)
     q = torch.empty((B * S, KVH * G * 128), dtype=x.dtype, device=x.device)
     ws = _gemm_workspace(x.device)
+    if w_panels is not None:   # wqkv once more as packing.pack_ring_panels lays it out (see gemm)
+        _chk(w_panels, "w_panels", torch.bfloat16)
+        assert w_panels.shape == wqkv.shape and x.dtype == torch.bfloat16
+        _lib.call("ullsam_gemm_qkv_rope_panels", dt_code(x.dtype), x.data_ptr(), K, wqkv.data_ptr(), K, w_panels.data_ptr(), _p(bias), B, S, K, KVH, G, pos.data_ptr(),
+                  cos_tab.data_ptr(), sin_tab.data_ptr(), cos_tab.shape[0], q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.shape[2],
+                  cache_pos0, ws.data_ptr(), ws.numel(), _stream())
+        return q
     _lib.call("ullsam_gemm_qkv_rope", dt_code(x.dtype), x.data_ptr(), K, wqkv.data_ptr(), K, _p(bias), B, S, K, KVH, G, pos.data_ptr(),
               cos_tab.data_ptr(), sin_tab.data_ptr(), cos_tab.shape[0], q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.shape[2],
               cache_pos0, ws.data_ptr(), ws.numel(), _stream())

@@ -12,6 +12,27 @@ def pack_w13(w1: torch.Tensor, w3: torch.Tensor) -> torch.Tensor:
     return torch.stack([w1.reshape(I // 64, 64, K), w3.reshape(I // 64, 64, K)], dim=1).reshape(2 * I, K).contiguous()
 
 
+def pack_ring_panels(w: torch.Tensor) -> torch.Tensor:
+    """[N, K] bf16 -> the same values ordered [N/16][K/32][16 rows][32 k] (the ring GEMM's K-panels, csrc/gemm_ring8p.h): weight row R,
+    element k sits at ((R // 16) * (K // 32) + k // 32) * 512 + (R % 16) * 32 + k % 32, so one (16-row block, 32-deep k step) cell is one
+    contiguous KiB -- what one LDS-DMA request of the kernel reads.  The result keeps the SHAPE [N, K] (callers derive FLOPs and bytes
+    from it) and starts on a 1 KiB boundary; unpack_ring_panels is the inverse."""
+    N, K = w.shape
+    if w.dtype != torch.bfloat16 or N % 16 != 0 or K % 32 != 0:
+        raise ValueError(f"pack_ring_panels: bf16 [N, K] with N % 16 == 0 and K % 32 == 0 needed, got {w.dtype} {tuple(w.shape)}")
+    buf = torch.empty(N * K + 512, dtype=w.dtype, device=w.device)   # (the caching allocator aligns to 512 bytes only)
+    skip = (-buf.data_ptr() % 1024) // 2
+    out = buf[skip:skip + N * K].view(N, K)
+    out.view(N // 16, K // 32, 16, 32).copy_(w.detach().reshape(N // 16, 16, K // 32, 32).permute(0, 2, 1, 3))
+    return out
+
+
+def unpack_ring_panels(p: torch.Tensor) -> torch.Tensor:
+    """The row-major [N, K] weight of pack_ring_panels' output."""
+    N, K = p.shape
+    return p.view(N // 16, K // 32, 16, 32).permute(0, 2, 1, 3).reshape(N, K).contiguous()
+
+
 def pack_conv3x3(w: torch.Tensor) -> torch.Tensor:
     """Conv2d weight [Cout, Cin, 3, 3] -> [Cout, (ky, kx, Cin)] matching ullsam_im2col3x3's column order."""
     return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
