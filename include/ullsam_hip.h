@@ -486,6 +486,27 @@ int ullsam_distance_columns(const int* labels, int H, int W, int feature, int ed
 int ullsam_distance_rows(const int* labels, const unsigned short* g, const int* nearest, int H, int W, int mode, int edge, long limit, int route,
                          long K, int* out0, int* out1, unsigned long long* best, int* flags, void* stream);
 int ullsam_distance_depth_decode(const unsigned long long* best, long K, int W, int* r2, int* xy, void* stream);
+/* The same transforms of a label volume with anisotropic voxels (csrc/distance3d.hip; integer work, bit-exact with the host forms of
+   utils.distance3d; definition in DESIGN.md "7b, continued (3-D distances)").  volume i32 [Z, H, W], 0 = background, 1 <= Z, H, W <= 32767,
+   Z * H * W <= 2^31 - 1.  (sz, sy, sx) in 1..46340: |p - q|^2 = sz^2 dz^2 + sy^2 dy^2 + sx^2 dx^2.  (ez, ey, ex): the voxels just outside the
+   volume along that axis count as another label (inner modes only; the feature modes need 0, 0, 0).  The y and x entries refuse
+   B = sum of s_a^2 (n_a - 1 + e_a)^2 > 2^31 - 2, so every finite result fits int32; INF = 2^31 - 1, 0xFFFF in the 16-bit map.  flags as above.
+   distance3d_z: feature = 0: g u16 [Z, H, W] = the distance in voxels from a labelled voxel to the end of its run of equal label along z,
+     plus 1 (0xFFFF where both ends are open; 0 on the background).  feature = 1: g = the distance in voxels to the nearest labelled voxel of
+     the (y, x) column (0xFFFF: none), nearest i32 [Z, H, W] = its label, the smaller of the two at equal distance (0 with 0xFFFF).
+   distance3d_y: feature = 0: h i32 [Z, H, W] = the inner distance within the (z, y) plane of the voxel (INF: none; 0 on the background),
+     hlabel is not touched.  feature = 1: (h, hlabel) = the distance to the nearest labelled voxel of that plane and the smallest label that
+     attains it.  No scan looks farther than floor(sqrt(limit) / sy) voxels; beyond limit h is some value above limit.
+   distance3d_x: the x pass over distance3d_y's maps with distance_rows' modes 0..4 (out0, out1 i32 [Z, H, W]; best u64 [K], the linear index
+     being (z * H + y) * W + x); the modes 0 and 4 need limit = INF.  No scan looks farther than floor(sqrt(limit) / sx) voxels.
+   distance3d_depth_decode: r2 i32 [K] = best >> 32, xyz i32 [K, 3] = (x, y, z) of the linear index; a zero word gives 0, (-1, -1, -1). */
+int ullsam_distance3d_z(const int* volume, int Z, int H, int W, int feature, int ez, long K, unsigned short* g, int* nearest, int* flags,
+                        void* stream);
+int ullsam_distance3d_y(const int* volume, const unsigned short* g, const int* nearest, int Z, int H, int W, int feature, int sz, int sy, int sx,
+                        int ez, int ey, int ex, long limit, int* h, int* hlabel, void* stream);
+int ullsam_distance3d_x(const int* volume, const int* h, const int* hlabel, int Z, int H, int W, int mode, int sz, int sy, int sx, int ez, int ey,
+                        int ex, long limit, long K, int* out0, int* out1, unsigned long long* best, int* flags, void* stream);
+int ullsam_distance3d_depth_decode(const unsigned long long* best, long K, int H, int W, int* r2, int* xyz, void* stream);
 /* Splitting the touching objects of a label image: a watershed of every instance's own depth map without a flood (csrc/split.hip; integer
    work, bit-exact with the host form utils.split.split_labels; definition in DESIGN.md "7b, continued (splitting)").  labels i32 [H, W] with ids
    0..K, 0 = background, 1 <= H, W <= 32767; d2 i32 [H, W] = distance_rows' mode 0 of the same labels; p = y * W + x, n = H * W;

@@ -114,6 +114,10 @@ SIGNATURES = {
     "ullsam_distance_columns": [vp, i32, i32, i32, i32, i64, vp, vp, vp, vp],
     "ullsam_distance_rows": [vp, vp, vp, i32, i32, i32, i32, i64, i32, i64, vp, vp, vp, vp, vp],
     "ullsam_distance_depth_decode": [vp, i64, i32, vp, vp, vp],
+    "ullsam_distance3d_z": [vp, i32, i32, i32, i32, i32, i64, vp, vp, vp, vp],
+    "ullsam_distance3d_y": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i64, vp, vp, vp],
+    "ullsam_distance3d_x": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i64, i64, vp, vp, vp, vp, vp],
+    "ullsam_distance3d_depth_decode": [vp, i64, i32, i32, vp, vp, vp],
     "ullsam_split_ascent": [vp, vp, i32, i32, i64, i32, vp, vp, vp],
     "ullsam_split_flatten": [vp, i64, i64, vp, vp],
     "ullsam_split_passes": [vp, vp, vp, i32, i32, i64, vp, vp, i64, i32, vp, vp],

@@ -1230,6 +1230,119 @@ def distance_depth_decode(best: torch.Tensor, w: int):
     return r2, xy
 
 
+# ---- the same transforms of a label volume with anisotropic voxels (csrc/distance3d.hip; utils.distance3d drives these) -----------------------
+DISTANCE3D_MAX_VOXELS = 2 ** 31 - 1   # the linear index of a voxel fits 32 bits (the depths' words)
+DISTANCE3D_MAX_SPACING = 46340        # s^2 < 2^31
+DISTANCE3D_MAX_B = 2 ** 31 - 2        # sum of s_a^2 (n_a - 1 + e_a)^2: every finite squared distance fits int32
+
+
+def _distance3d_volume(volume: torch.Tensor, num, what: str):
+    _chk(volume, "volume", torch.int32)
+    assert volume.dim() == 3, tuple(volume.shape)
+    z, h, w = volume.shape
+    if not all(1 <= n <= DISTANCE_MAX_SIDE for n in (z, h, w)) or z * h * w > DISTANCE3D_MAX_VOXELS:
+        raise _lib.UllsamError(f"{what}: a volume of {z} x {h} x {w} (each side in 1..{DISTANCE_MAX_SIDE}, at most 2^31 - 1 voxels)")
+    k = DISTANCE_INF if num is None else int(num)
+    if not 0 <= k <= DISTANCE_INF:
+        raise _lib.UllsamError(f"{what}: num = {num} must lie in 0..2^31 - 1")
+    return z, h, w, k
+
+
+def _distance3d_metric(shape, spacing, edge, what: str):
+    s = tuple(int(v) for v in spacing)
+    e = tuple(int(bool(v)) for v in edge)
+    if len(s) != 3 or len(e) != 3 or not all(1 <= v <= DISTANCE3D_MAX_SPACING for v in s):
+        raise _lib.UllsamError(f"{what}: spacing {spacing!r} and edge {edge!r} must be triples (z, y, x), each spacing in 1..{DISTANCE3D_MAX_SPACING}")
+    b = sum(v * v * (n - 1 + ea) ** 2 for v, n, ea in zip(s, shape, e))
+    if b > DISTANCE3D_MAX_B:
+        raise _lib.UllsamError(f"{what}: the largest squared distance {b} must be at most 2^31 - 2")
+    return s, e
+
+
+def _distance3d_limit(limit, what: str) -> int:
+    lim = DISTANCE_INF if limit is None else int(limit)
+    if not 0 <= lim <= DISTANCE_INF:
+        raise _lib.UllsamError(f"{what}: limit = {limit} must lie in 0..2^31 - 1")
+    return lim
+
+
+def distance3d_z(volume: torch.Tensor, feature: bool = False, edge: bool = False, num: Optional[int] = None, flags: Optional[torch.Tensor] = None):
+    """volume int32 [Z, H, W] -> (g uint16 [Z, H, W], nearest int32 [Z, H, W] or None, flags): the z pass (ullsam_hip.h distance3d_z), in voxels.  feature
+    False: g = the distance of a labelled voxel to the end of its run of equal label along z, plus 1 (edge: the z edge counts); True: to the nearest
+    labelled voxel of the column, whose label is `nearest`.  0xFFFF = none.  flags as in distance_columns."""
+    z, h, w, k = _distance3d_volume(volume, num, "distance3d_z")
+    dev = volume.device
+    g = torch.empty((z, h, w), dtype=torch.uint16, device=dev)
+    nearest = torch.empty((z, h, w), dtype=torch.int32, device=dev) if feature else None
+    flags = _distance_flags(flags, dev)
+    _lib.call("ullsam_distance3d_z", volume.data_ptr(), z, h, w, int(bool(feature)), int(bool(edge)), k, g.data_ptr(), _p(nearest), flags.data_ptr(), _stream())
+    return g, nearest, flags
+
+
+def distance3d_y(volume: torch.Tensor, g: torch.Tensor, nearest: Optional[torch.Tensor], spacing=(1, 1, 1), edge=(False, False, False),
+                 limit: Optional[int] = None):
+    """The y pass over distance3d_z's maps (ullsam_hip.h distance3d_y) -> (h int32 [Z, H, W], hlabel int32 [Z, H, W] or None).  nearest None: the
+    inner distance within every (z, y) plane; otherwise the distance to the nearest labelled voxel of the plane and the smallest label that attains
+    it.  spacing, edge: triples (z, y, x).  limit None = unbounded; otherwise no scan looks farther than floor(sqrt(limit) / sy) voxels."""
+    z, h, w, _ = _distance3d_volume(volume, None, "distance3d_y")
+    feature = nearest is not None
+    s, e = _distance3d_metric((z, h, w), spacing, edge, "distance3d_y")
+    lim = _distance3d_limit(limit, "distance3d_y")
+    dev = volume.device
+    _chk(g, "g", torch.uint16)
+    assert tuple(g.shape) == (z, h, w), tuple(g.shape)
+    if feature:
+        _chk(nearest, "nearest", torch.int32)
+        assert tuple(nearest.shape) == (z, h, w), tuple(nearest.shape)
+    out = torch.empty((z, h, w), dtype=torch.int32, device=dev)
+    hlabel = torch.empty((z, h, w), dtype=torch.int32, device=dev) if feature else None
+    _lib.call("ullsam_distance3d_y", volume.data_ptr(), g.data_ptr(), _p(nearest), z, h, w, int(feature), *s, *e, lim, out.data_ptr(), _p(hlabel), _stream())
+    return out, hlabel
+
+
+def distance3d_x(volume: torch.Tensor, h: torch.Tensor, hlabel: Optional[torch.Tensor], mode: str, spacing=(1, 1, 1), edge=(False, False, False),
+                 limit: Optional[int] = None, num: Optional[int] = None, flags: Optional[torch.Tensor] = None):
+    """The x pass over distance3d_y's maps (ullsam_hip.h distance3d_x) -> (outputs, flags), with distance_rows' modes: "inner": D2 int32 [Z, H, W];
+    "feature": (D2, nearest label), (INF, 0) beyond limit; "expand": the labels grown by limit = r2; "shrink": the labels whose D2 > limit = r2;
+    "depth": best int64 [num] (distance3d_depth_decode reads it).  limit None = unbounded (required for "inner" and "depth")."""
+    z, hh, w, k = _distance3d_volume(volume, num, "distance3d_x")
+    m = DISTANCE_MODES[mode]
+    feat = mode in ("feature", "expand")
+    s, e = _distance3d_metric((z, hh, w), spacing, edge, "distance3d_x")
+    lim = _distance3d_limit(limit, "distance3d_x")
+    dev = volume.device
+    _chk(h, "h", torch.int32)
+    assert tuple(h.shape) == (z, hh, w), tuple(h.shape)
+    if feat:
+        _chk(hlabel, "hlabel", torch.int32)
+        assert tuple(hlabel.shape) == (z, hh, w), tuple(hlabel.shape)
+    flags = _distance_flags(flags, dev)
+    out0 = out1 = best = None
+    if mode == "depth":
+        if num is None or k > MOSAIC_MAX_IDS:
+            raise _lib.UllsamError("distance3d_x: the depths need num in 0..2^31 - 2")
+        best = torch.empty((k,), dtype=torch.int64, device=dev)
+    else:
+        out0 = torch.empty((z, hh, w), dtype=torch.int32, device=dev)
+        if mode == "feature":
+            out1 = torch.empty((z, hh, w), dtype=torch.int32, device=dev)
+    _lib.call("ullsam_distance3d_x", volume.data_ptr(), h.data_ptr(), _p(hlabel) if feat else None, z, hh, w, m, *s, *e, lim, k, _p(out0), _p(out1), _p(best),
+              flags.data_ptr(), _stream())
+    out = best if mode == "depth" else ((out0, out1) if mode == "feature" else out0)
+    return out, flags
+
+
+def distance3d_depth_decode(best: torch.Tensor, h: int, w: int):
+    """best int64 [K] (distance3d_x's "depth" output) of a volume of height h and width w -> (r2 int32 [K], xyz int32 [K, 3]); an absent id: 0 and
+    (-1, -1, -1)."""
+    _chk(best, "best", torch.int64)
+    k = best.numel()
+    r2 = torch.empty((k,), dtype=torch.int32, device=best.device)
+    xyz = torch.empty((k, 3), dtype=torch.int32, device=best.device)
+    _lib.call("ullsam_distance3d_depth_decode", best.data_ptr(), k, int(h), int(w), r2.data_ptr(), xyz.data_ptr(), _stream())
+    return r2, xyz
+
+
 # ---- splitting the touching objects of a label image (csrc/split.hip; utils.split drives these) -----------------------------------------------
 SPLIT_FLAGS = 8            # bad id / entry, pair refused, pairs claimed, chain too long, representatives counted, list cursor, (two free)
 SPLIT_MAX_DEPTH = 32767
