@@ -44,7 +44,9 @@ int ullsam_set_gemm_variant(int variant);
    identical trips, both wave groups' epilogues together; 0 = one tile per workgroup (the kernel of rounds 2 - 5); every other value is rejected;
    key 3 = split-K on the ring kernel for launches of <= 128 tiles whose K cuts into ranges of >= 1280 that fill >= 224 workgroups: 1 (default) = where the caller allows it
    (ullsam_gemm's act | 256), 0 = never, 2 = wherever it fits;
-   key 4 = the weight as K-panels (ullsam_gemm_panels): 1 (default) = ring launches that were handed panels read them, 0 = every launch reads the row-major weight (bit-equal) */
+   key 4 = the weight as K-panels (ullsam_gemm_panels): 1 (default) = ring launches that were handed panels read them, 0 = every launch reads the row-major weight (bit-equal);
+   key 5 = activations as K-panels (ullsam_gemm_act_panels): 1 (default) = ring launches take the a_panels / out_panels flags where the query says so, 0 = the query
+   answers no and a flag is refused, i.e. every launch runs as it did before the flags existed (bit-equal) */
 int ullsam_set_gemm_tuning(int key, int value);
 /* Attention kernel selection for A/B measurements and the kernel tests: 0 = production; 1 / 2 = windowed attention on the tiled kernel (7-wave /
    4-wave workgroups) instead of the whole-window kernel; 3..8 = start stagger of the whole-window kernel's second resident workgroup; 9 = global
@@ -88,6 +90,26 @@ int ullsam_gemm_panels(int dtype, const void* A, long lda, const void* W, long l
 int ullsam_gemm_qkv_rope_panels(int dtype, const void* A, long lda, const void* W, long ldw, const void* w_panels, const float* bias, int B, int S,
                                 int K, int KVH, int G, const int* pos, const float* cos_tab, const float* sin_tab, int tab_rows, void* q_out,
                                 void* k_cache, void* v_cache, int cap, int cache_pos0, void* workspace, long ws_bytes, void* stream);
+
+/* ... and with the bf16 ACTIVATIONS as K-panels: [ceil(M / 16)][K / 32][16 rows][32 k] (ullsam_amd.packing.pack_activation_panels: the cell of the weight
+ * panels, the row count rounded up to 16; 1 KiB aligned; rows M .. the next multiple of 16 exist, are never written and never reach a stored value).  The
+ * layout is written by the kernel that PRODUCES the activation -- the norm in front of wqkv / w13 (modeling_internlm2.py:598-618) and of qkv / lin1
+ * (image_encoder.py:166,180), the SwiGLU epilogue of w13 in front of w2 (modeling_internlm2.py:261-264), the GELU epilogue of lin1 in front of lin2
+ * (common.py:23-25) -- never by a repacking pass.  a_panels: A is laid out so (lda == K).  out_panels: C is written so (2-byte outputs without residual:
+ * plain, bias, GELU / ReLU, SwiGLU; N_out % 32 == 0, ldc == N_out).  Only the two ring kernels take the flags: ask ullsam_gemm_act_panels_query for the launch
+ * first; a flag on a launch that does not take it is an error before anything is launched.  w_panels is nullable.  Same result bit for bit. */
+int ullsam_gemm_act_panels(int dtype, const void* A, long lda, const void* W, long ldw, const void* w_panels, void* C, long ldc, int out_f32,
+                           const float* bias, const float* residual, long ldr, int res_row_mod, int act, int M, int N, int K,
+                           void* workspace, long ws_bytes, int a_panels, int out_panels, void* stream);
+/* modeling_internlm2.py:359-388 as ullsam_gemm_qkv_rope_panels, reading A as panels; q / k / v stay row-major */
+int ullsam_gemm_qkv_rope_act_panels(int dtype, const void* A, long lda, const void* W, long ldw, const void* w_panels, const float* bias, int B, int S,
+                                    int K, int KVH, int G, const int* pos, const float* cos_tab, const float* sin_tab, int tab_rows, void* q_out,
+                                    void* k_cache, void* v_cache, int cap, int cache_pos0, void* workspace, long ws_bytes, int a_panels, void* stream);
+/* Would this launch read A as panels, could it write C as panels?  Runs the dispatch of the launch itself and launches nothing.  The launch as the modules make
+ * it: contiguous operands, act as for ullsam_gemm (4 = the wqkv + RoPE launch with N = KVH (G + 2) 128), ws_bytes of workspace, aligned = A and C on 1 KiB
+ * boundaries, bias / residual on 16-byte ones. */
+int ullsam_gemm_act_panels_query(int dtype, int M, int N, int K, int act, int out_f32, int has_bias, int has_residual, int aligned, long ws_bytes,
+                                 int* reads_a_panels, int* writes_c_panels);
 
 /* Decode step (InternVLSAMModel.generate's token loop, modeling_internlm2.py:1112-1149; M <= 4 rows, bf16 weights): the RMSNorm that
  * precedes a layer's wqkv / w13 (modeling_internlm2.py:75-89, 598-618) folded into the GEMM that consumes it:
@@ -206,6 +228,10 @@ int ullsam_train_index_add_rows(const float* src, const int* idx, float* dst, lo
 int ullsam_norm(const void* in, int in_dtype, long in_stride, void* out, int out_dtype, long out_stride, const float* w,
                 const float* b, long rows, int D, float eps, int rms, int act, const float* post_scale,
                 const float* post_shift, void* stream);
+/* ullsam_norm with a bf16 output written as activation K-panels for the GEMM that follows (image_encoder.py:166,180; modeling_internlm2.py:598-618): out is the
+ * 1 KiB aligned buffer of ceil(rows / 16) * 16 rows of D elements, D % 32 == 0.  out_panels == 0: row-major with stride D.  Same values, only where each goes. */
+int ullsam_norm_panels(const void* in, int in_dtype, long in_stride, void* out, const float* w, const float* b, long rows, int D, float eps, int rms,
+                       int act, const float* post_scale, const float* post_shift, int out_panels, void* stream);
 int ullsam_set_norm_variant(int v);   /* developer switch: non-zero = wave-per-row kernel for every shape (A/B) */
 
 /* LayerNorm whose result feeds three consumers at once: fp32 stream, compute-dtype copy, compute-dtype (y + pe[row % pe_rows]).

@@ -2,12 +2,13 @@
 drift with load, so only interleaved rounds in one process compare two dispatch policies.
 usage: python tools/step_ab.py [rounds] [maskA,maskB,...]     ring tile shapes the auto dispatch may pick (ullsam_set_gemm_tuning key 1):
 0 two-buffer / 128x128 kernels only, bit 0 256x256 ring, bit 1 256x320 ring, bit 2 272x256 ring (default 7); suffixes select the other knobs, e.g. "7w0" = the ring
-kernels read the row-major weights instead of the K-panels ("7w0,7,7w0v0": the layout A/B with an A/A pair -- the last variant is the first under another name)"""
+kernels read the row-major weights instead of the K-panels ("7w0,7,7w0v0": the layout A/B with an A/A pair -- the last variant is the first under another name);
+"7x0" = activations stay row-major (ops.set_activation_panels(False): the step as it ran before producers wrote K-panels), so "7x0,7,7x0v0" is that layout's A/B with its A/A pair"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
-from ullsam_amd import _lib
+from ullsam_amd import _lib, ops
 
 
 def main():
@@ -25,7 +26,9 @@ def main():
         times = {v: [] for v in variants}
         for r in range(rounds):
             for v in (variants if r % 2 == 0 else variants[::-1]):   # ABBA: the variant measured second in a round comes out ~0.5 % faster
-                head, _, wl = str(v).partition("w")     # "7w0" = dispatch mask 7 with the K-panel copies of the weights ignored (ullsam_set_gemm_tuning key 4: 0 row-major, 1 panels = the default); the suffix comes first: "7w0v0"
+                head, _, xl = str(v).partition("x")     # "7x0" = dispatch mask 7 with row-major activations (ullsam_set_gemm_tuning key 5 and the modules' plan: 0 off, 1 K-panels = the default); the digit, then the other suffixes
+                ops.set_activation_panels(not xl.startswith("0"))
+                head, _, wl = (head + xl[1:]).partition("w")     # "7w0" = dispatch mask 7 with the K-panel copies of the weights ignored (ullsam_set_gemm_tuning key 4: 0 row-major, 1 panels = the default); the suffix comes first: "7w0v0"
                 wl, _, tail = wl.partition("v")
                 lib.ullsam_set_gemm_tuning(4, int(wl) if wl else 1)
                 head = head + ("v" + tail if tail else "")
@@ -52,6 +55,7 @@ def main():
     lib.ullsam_set_gemm_tuning(0, 4)
     lib.ullsam_set_gemm_tuning(2, 2)
     lib.ullsam_set_gemm_tuning(4, 1)
+    ops.set_activation_panels(True)
     for v in variants:
         t = sorted(times[v])
         print(f"dispatch mask {v}: median {t[len(t) // 2]:.3f} ms/step  (min {t[0]:.3f}, max {t[-1]:.3f})  = {4e3 / t[len(t) // 2]:.2f} images/s")

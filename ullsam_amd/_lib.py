@@ -22,6 +22,9 @@ SIGNATURES = {
     "ullsam_gemm_qkv_rope": [i32, vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i64, vp],
     "ullsam_gemm_panels": [i32, vp, i64, vp, i64, vp, vp, i64, i32, vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, vp],
     "ullsam_gemm_qkv_rope_panels": [i32, vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i64, vp],
+    "ullsam_gemm_act_panels": [i32, vp, i64, vp, i64, vp, vp, i64, i32, vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, i32, i32, vp],
+    "ullsam_gemm_qkv_rope_act_panels": [i32, vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i64, i32, vp],
+    "ullsam_gemm_act_panels_query": [i32, i32, i32, i32, i32, i32, i32, i32, i32, i64, vp, vp],
     "ullsam_gemm_rmsnorm": [vp, i64, vp, f32, vp, i64, vp, i64, i32, vp, vp, i64, i32, i32, i32, i32, vp],
     "ullsam_decode_qkv_rope": [vp, vp, i64, vp, f32, vp, i64, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp],
     "ullsam_train_matmul": [vp, vp, vp, i32, i32, i32, i32] + [i64] * 9 + [i32, vp],
@@ -47,6 +50,7 @@ SIGNATURES = {
     "ullsam_train_embedding_bwd": [vp, i64, vp, vp, vp, i64, i32, i32, i32, vp, i32, vp],
     "ullsam_train_index_add_rows": [vp, vp, vp, i64, i32, i32, vp],
     "ullsam_norm": [vp, i32, i64, vp, i32, i64, vp, vp, i64, i32, f32, i32, i32, vp, vp, vp],
+    "ullsam_norm_panels": [vp, i32, i64, vp, vp, vp, i64, i32, f32, i32, i32, vp, vp, i32, vp],
     "ullsam_norm_fanout": [vp, i64, i32, vp, vp, f32, vp, vp, vp, i32, vp, i64, vp],
     "ullsam_vit_attention": [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "ullsam_causal_attention": [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],

@@ -63,6 +63,11 @@ struct GemmArgs {
     const float* norm_x; const float* norm_w; float norm_eps; long ldx;
     const void* w_panels;   // the weight once more as K-panels (packing.pack_ring_panels), or null: read by the ring kernels where launch_ring keeps it
     int group_m;     // tile rows per raster group of the 256-row-tile kernels (tiles of a group run column-major: group_m x tiles_n); 4 by default
+    // Activation K-panels (packing.pack_activation_panels: bf16 [ceil(M / 16)][K / 32][16 rows][32 k], the weight panels' cell with the row count rounded up to 16).
+    // a_panels: A is laid out so (lda == K); out_panels: the direct 2-byte epilogues write C so ([ceil(M / 16)][N_out / 32][16][32]).  Ring kernels only: every
+    // other route refuses a launch that carries either flag (gemm_impl), so a panel buffer is never read or written as row-major.
+    int a_panels, out_panels;
+    int* plan;       // query (ullsam_gemm_act_panels_query): the dispatch runs as for a launch, writes {reads A as panels, can write C as panels} here and launches nothing
 };
 
 #ifndef ULLSAM_RING_ASM_DMA
@@ -794,6 +799,10 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
     const bool panels = EMODE != 2 && p.w_panels != nullptr;
     const unsigned int kst = __builtin_amdgcn_readfirstlane(panels ? 1024u : 64u);   // bytes of W from one stage to the next
     const char* b_base = reinterpret_cast<const char*>(panels ? p.w_panels : p.W) + (size_t)n0 * p.ldw * 2;
+    // The activation as K-panels (p.a_panels, kept by launch_ring where lda == K): the same remedy for the other operand.  m0 is a multiple of 16 and a 16-row
+    // block is 16 K elements, so the tile's base keeps its form as well.
+    const bool a_pan = EMODE != 2 && p.a_panels != 0;
+    const unsigned int akst = __builtin_amdgcn_readfirstlane(a_pan ? 1024u : 64u);   // bytes of A from one stage to the next
     const int na = (PA - wave + 7) / 8, nb = (PB - wave + 7) / 8;
     // The MFMA operands are SWAPPED (weight fragment first), so a lane's four accumulator registers of a sub-tile are four consecutive COLUMNS
     // of one output row and the epilogue can store straight from the accumulators; for 2-byte outputs the weight rows of a wave are permuted on
@@ -815,7 +824,12 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
     for (int i = 0; i < 3; ++i) {
         const int row = (wave + 8 * i) * 16 + (lane >> 2);
         const int c = (lane & 3) ^ ((row >> 2) & 2);
-        a_off[i] = (unsigned int)((size_t)(min(m0 + row, p.M - 1) - m0) * p.lda * 2) + (c << 4);
+        if (a_pan) {   // rows past M inside the last 16-row block exist in the buffer (never written, feeding accumulator rows >= M only); whole blocks past it clamp to its last row
+            const int ar = min(m0 + row, ((p.M + 15) & ~15) - 1) - m0;
+            a_off[i] = (unsigned int)(ar >> 4) * ((unsigned int)p.K * 32u) + (unsigned int)(ar & 15) * 64u + (c << 4);
+        } else {
+            a_off[i] = (unsigned int)((size_t)(min(m0 + row, p.M - 1) - m0) * p.lda * 2) + (c << 4);
+        }
         const int wr = w_row(row);
         b_off[i] = panels ? (unsigned int)(wr >> 4) * ((unsigned int)p.K * 32u) + (unsigned int)(wr & 15) * 64u + (c << 4)
                           : (unsigned int)((size_t)(min(n0 + wr, p.N - 1) - n0) * p.ldw * 2) + (c << 4);
@@ -832,7 +846,7 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
 
     auto stage = [&](int s) {   // request stage s into ring slot s & 3
         char* base = smem + (s & 3) * STG;
-        const char* ak = a_base + (size_t)s * 64;
+        const char* ak = a_base + (size_t)s * akst;
         const char* bk = b_base + (size_t)s * kst;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -893,7 +907,7 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
             Frag<T> a8[MI], b[NTW];
             {
                 char* base = smem + ((s + 2) & 3) * STG;
-                const char* ak = a_base + (size_t)(s + 2) * 64;
+                const char* ak = a_base + (size_t)(s + 2) * akst;
                 const char* bk = b_base + (size_t)(s + 2) * kst;
                 auto request = [&](int qi) __attribute__((always_inline)) {   // request qi of this wave: A0 B0 A1 B1 A2 B2 (qi is a constant after unrolling)
                     const int i = qi >> 1;
@@ -975,6 +989,16 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
         const int rowp = row0 & ~1;   // after pair_swap the lane pair (mm, mm ^ 1) owns rows rowp + 16 i and rowp + 16 i + 1
         const bool direct = p.vec_ok && (p.N & 7) == 0 && (p.M & 1) == 0 && (p.out_f32 || !p.residual);   // (the direct 2-byte epilogues add no residual)
         auto gst = [&](void* ptr, u32x4 v) __attribute__((always_inline)) { *reinterpret_cast<u32x4*>(ptr) = v; };
+        // C as activation K-panels (p.out_panels, the direct 2-byte epilogues only): element (row, col) of the [M, n_out] output sits in cell (row / 16, col / 32) at
+        // (row % 16) * 32 + col % 32.  Every store below is 8 or 16 bytes at a column that is a multiple of 4 or 8 -- whatever the row permutation (w_row) and for the fifth
+        // sub-tile of a 320-wide tile (WW = 80 = 2 x 32 + 16) alike -- so it never crosses a 32-column cell; tile rows start at multiples of 16, so sub-tile row i is cell
+        // row i further and the lane pair's second row 32 elements further.  o_r16 / o_r1: elements from a row to the row 16 / 1 below it.
+        const bool o_pan = p.out_panels != 0;
+        const size_t o_cells = (size_t)((p.act == 3 ? p.N >> 1 : p.N) >> 5);
+        const size_t o_r16 = o_pan ? o_cells * 512 : (size_t)16 * p.ldc, o_r1 = o_pan ? (size_t)32 : (size_t)p.ldc;
+        auto o_at = [&](int row, int col) __attribute__((always_inline)) -> size_t {
+            return o_pan ? ((size_t)(row >> 4) * o_cells + (size_t)(col >> 5)) * 512 + (size_t)((row & 15) * 32 + (col & 31)) : (size_t)row * p.ldc + col;
+        };
         if constexpr (EMODE == 1) {
             // wqkv + RoPE + KV-cache append (modeling_internlm2.py:359-388, 233-247), straight from the accumulators.  The tile's 256 columns are two
             // 128-wide head slots; with the SwiGLU-style row permutation this lane holds, of output row row0 + 16 i, columns d .. d + 7 of a slot
@@ -1034,9 +1058,9 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
             // bf16 (+bias, +GELU / ReLU): sub-tiles (2 h, 2 h + 1) are this lane's 8 columns of the 32-column group h; the two groups are 128 contiguous
             // bytes of a row -> pair_swap; the fifth sub-tile of a 320-wide tile is 4 columns (8 bytes) of the lane's own row
             const int colb = n0 + wn * WW + (odd ? 32 : 0) + 8 * g4;
-            T* cp = reinterpret_cast<T*>(p.C) + (size_t)rowp * p.ldc + colb;
+            T* cp = reinterpret_cast<T*>(p.C) + o_at(rowp, colb);
             const int col5 = n0 + wn * WW + 64 + 4 * g4;
-            T* cp5 = reinterpret_cast<T*>(p.C) + (size_t)row0 * p.ldc + col5;
+            T* cp5 = reinterpret_cast<T*>(p.C) + o_at(row0, col5);
             auto drain = [&](auto ACT) __attribute__((always_inline)) {
                 uint2 w5 = make_uint2(0u, 0u);   // (NTW == 5) the even sub-tile row's fifth sub-tile, waiting for its odd partner
                 auto actf = [&](float v) __attribute__((always_inline)) {
@@ -1057,8 +1081,8 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
                     u32x4 s0, s1;
                     pair_swap((u32x4){o[0], o[1], o[2], o[3]}, (u32x4){o[4], o[5], o[6], o[7]}, odd, s0, s1);
                     if (rowp + 16 * i < p.M && colb < p.N) {   // M is even: both rows of the pair or neither
-                        gst(cp + (size_t)(16 * i) * p.ldc, s0);
-                        gst(cp + (size_t)(16 * i + 1) * p.ldc, s1);
+                        gst(cp + i * o_r16, s0);
+                        gst(cp + i * o_r16 + o_r1, s1);
                     }
                     if constexpr (NTW == 5) {
                         // the fifth sub-tile: 4 columns (8 bytes) of the lane's own row.  Sub-tile rows (i, i + 1) trade across the 16-lane rows
@@ -1074,12 +1098,12 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
                                 const auto ry = __builtin_amdgcn_permlane16_swap(w5.y, w.y, false, false);
                                 const int r5 = row0 + 16 * (i - 1 + (g4 & 1));
                                 if (r5 < p.M && col5 < p.N)
-                                    gst(reinterpret_cast<T*>(p.C) + (size_t)r5 * p.ldc + (n0 + wn * WW + 64 + 8 * (g4 >> 1)), (u32x4){rx[0], ry[0], rx[1], ry[1]});
+                                    gst(reinterpret_cast<T*>(p.C) + o_at(r5, n0 + wn * WW + 64 + 8 * (g4 >> 1)), (u32x4){rx[0], ry[0], rx[1], ry[1]});
                             } else {
                                 w5 = w;
                             }
                         } else {
-                            if (row0 + 16 * i < p.M && col5 < p.N) *reinterpret_cast<uint2*>(cp5 + (size_t)(16 * i) * p.ldc) = w;
+                            if (row0 + 16 * i < p.M && col5 < p.N) *reinterpret_cast<uint2*>(cp5 + i * o_r16) = w;
                         }
                     }
                 }
@@ -1089,7 +1113,7 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
             else drain(std::integral_constant<int, 0>{});
         } else if (NTW == 4 && direct && !p.out_f32 && p.act == 3) {
             // SwiGLU: out[:, n0/2 + 64 (wn >> 1) + 32 (wn & 1) + 8 g4 + e] = silu(gate_e) * up_e, gate = sub-tiles 0 / 1, up = 2 / 3 (modeling_internlm2.py:261-264)
-            T* cp = reinterpret_cast<T*>(p.C) + (size_t)row0 * p.ldc + (n0 >> 1) + (wn >> 1) * 64 + (wn & 1) * 32 + 8 * g4;
+            T* cp = reinterpret_cast<T*>(p.C) + o_at(row0, (n0 >> 1) + (wn >> 1) * 64 + (wn & 1) * 32 + 8 * g4);
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
                 if (!(i < MI1 || i < mi)) continue;
@@ -1102,7 +1126,7 @@ __global__ __launch_bounds__(512) void gemm_ring8_kernel(GemmArgs p) {
                     // result is rounded to bf16 two lines below (gated to 1e-5 of the exact form by tests/test_kernels_gpu.py)
                     o[q] = pack_bf16x2(g0 * __builtin_amdgcn_rcpf(1.0f + __expf(-g0)) * u0, g1 * __builtin_amdgcn_rcpf(1.0f + __expf(-g1)) * u1);
                 }
-                if (row0 + 16 * i < p.M) gst(cp + (size_t)(16 * i) * p.ldc, (u32x4){o[0], o[1], o[2], o[3]});
+                if (row0 + 16 * i < p.M) gst(cp + i * o_r16, (u32x4){o[0], o[1], o[2], o[3]});
             }
         } else if (direct && p.out_f32 && p.act == 0) {
             // fp32 residual stream: C = acc + bias + residual[row (mod res_row_mod)]; sub-tiles (2 jp, 2 jp + 1) are 128 contiguous bytes of a row
@@ -1257,7 +1281,7 @@ static int launch_gemm_ring_splitk(const GemmArgs& a, int S, hipStream_t stream)
     static PerDeviceOnce attr_set;
     if (attr_set.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring8_kernel<MI0, MI1, NTW, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     GemmArgs b = a;
-    b.C = a.ws; b.ldc = a.N; b.out_f32 = 1; b.bias = nullptr; b.residual = nullptr; b.act = 0; b.vec_ok = 1; b.dbg = nullptr; b.w_panels = nullptr;   // (a K range of panels is not a panel matrix)
+    b.C = a.ws; b.ldc = a.N; b.out_f32 = 1; b.bias = nullptr; b.residual = nullptr; b.act = 0; b.vec_ok = 1; b.dbg = nullptr; b.w_panels = nullptr; b.a_panels = b.out_panels = 0;   // (a K range of panels is not a panel matrix)
     b.tiles_m = (a.M + BM - 1) / BM;
     b.tiles_n = (a.N + BN - 1) / BN;
     b.full_tiles = b.tiles_m * b.tiles_n;
@@ -1293,6 +1317,7 @@ static int ring_splitk_plan(const GemmArgs& a, int* shape) {
 // launches, ragged N, K not a multiple of 128, the LDS-staged epilogues -- stays on the one-tile-per-workgroup kernel.
 static int g_persist = 2;      // ullsam_set_gemm_tuning(2, v): 0 one tile per workgroup; 2 (default) persistent ring, uniform trips, both groups' epilogues together (-0.5 % of the bench step, outputs bit-equal).  No other value: the earlier persistent forms and the ablations that 1 and 4 - 7 selected are gone
 static int g_ring_panels = 1;  // ullsam_set_gemm_tuning(4, v): 1 (default) = a ring launch that was handed the weight as K-panels reads it (launch_ring); 0 = every launch reads the row-major weight (A/B, bit-equal)
+static int g_act_panels = 1;   // ullsam_set_gemm_tuning(5, v): 1 (default) = the ring launches take activations as K-panels (a_panels / out_panels) where launch_ring defines the layout; 0 = none does, the query answers no and a launch that carries a flag is refused: every launch then behaves as before the flags existed (A/B, bit-equal)
 static int cu_count() {
     static int n[32] = {};
     int d = 0;
@@ -1317,6 +1342,18 @@ static int launch_ring(const GemmArgs& a0, hipStream_t stream) {
     // K-panels only where the layout is defined and the row-major path neither clamps nor range-checks a weight row: whole tiles of a contiguous weight
     GemmArgs a = a0;
     if (!(g_ring_panels && a.N % (64 * NTW) == 0 && a.K % 32 == 0 && a.ldw == a.K)) a.w_panels = nullptr;
+    // Activation K-panels where the layout is defined: A for a contiguous, 1 KiB-aligned bf16 activation (not the split-K form: a K range of panels is not a panel
+    // matrix); C for the direct 2-byte epilogues (the condition of gemm_ring8_kernel's direct branches, which is all the persistent kernel takes) on a contiguous,
+    // 1 KiB-aligned output of whole 32-column cells.  The query (a.plan) gets the same two answers a launch is held to.
+    const int n_out = a.act == 3 ? a.N / 2 : a.N;
+    const bool a_ok = g_act_panels && EMODE != 2 && a.K % 32 == 0 && a.lda == a.K && ((uintptr_t)a.A & 1023) == 0;
+    const bool c_ok = g_act_panels && EMODE == 0 && !a.out_f32 && !a.residual && a.vec_ok && (a.N & 7) == 0 && (a.M & 1) == 0 && (a.act != 3 || NTW == 4) &&
+                      n_out % 32 == 0 && a.ldc == n_out && ((uintptr_t)a.C & 1023) == 0;
+    if (a.plan) { a.plan[0] = a_ok; a.plan[1] = c_ok; return 0; }
+    if ((a.a_panels && !a_ok) || (a.out_panels && !c_ok)) {
+        ullsam_set_error("ullsam_gemm: activation K-panels refused (A %d, C %d): this launch reads A as panels %d, can write C as panels %d -- ask the query first", a.a_panels, a.out_panels, (int)a_ok, (int)c_ok);
+        return -1;
+    }
     return ring_persist_ok<16 * (MI0 + MI1), 64 * NTW, NTW, EMODE>(a) ? launch_gemm_ring8p<MI0, MI1, NTW, EMODE>(a, stream, cu_count())
                                                                       : launch_gemm_ring8<MI0, MI1, NTW, EMODE>(a, stream);
 }
@@ -1476,7 +1513,7 @@ extern "C" int ullsam_gemm_fp8(const void* A8, long lda, const float* a_scale, c
     a.group_m = 4;   // gemm256f8_kernel rasters with a fixed group height
     a.vec_ok = vec ? 1 : 0;
     a.ws = nullptr; a.ws_bytes = 0; a.ksplit = 1;
-    a.row_scale = a_scale; a.col_scale = w_scale; a.dbg = nullptr; a.w_panels = nullptr;
+    a.row_scale = a_scale; a.col_scale = w_scale; a.dbg = nullptr; a.w_panels = nullptr; a.a_panels = a.out_panels = 0; a.plan = nullptr;
     a.tiles_m = (M + 255) / 256; a.tiles_n = (N + 255) / 256; a.full_tiles = a.tiles_m * a.tiles_n;
     static PerDeviceOnce attr_set;
     if (attr_set.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256f8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
@@ -1492,6 +1529,7 @@ extern "C" int ullsam_set_gemm_tuning(int key, int value) {
     if (key == 2 && (value == 0 || value == 2)) { g_persist = value; return 0; }
     if (key == 3 && value >= 0 && value <= 2) { g_ring_splitk = value; return 0; }
     if (key == 4 && (value == 0 || value == 1)) { g_ring_panels = value; return 0; }
+    if (key == 5 && (value == 0 || value == 1)) { g_act_panels = value; return 0; }
     ullsam_set_error("ullsam_set_gemm_tuning: unknown key %d / bad value %d", key, value);
     return -1;
 }
@@ -2103,7 +2141,8 @@ struct NormPrologue { const float* x; long ldx; const float* w; float eps; };
 
 static int gemm_impl(int dtype, const void* A, long lda, const void* W, long ldw, void* C, long ldc, int out_f32,
                      const float* bias, const float* residual, long ldr, int res_row_mod, int act, int M, int N,
-                     int K, void* workspace, long ws_bytes, void* stream, const RopeEpilogue* rope, const NormPrologue* norm = nullptr, const void* w_panels = nullptr) {
+                     int K, void* workspace, long ws_bytes, void* stream, const RopeEpilogue* rope, const NormPrologue* norm = nullptr, const void* w_panels = nullptr,
+                     int a_panels = 0, int out_panels = 0, int* plan = nullptr) {
     ULLSAM_CHECK(dtype == ULLSAM_DT_F32 || dtype == ULLSAM_DT_BF16, "ullsam_gemm: bad dtype %d", dtype);
     ULLSAM_CHECK(M > 0 && N > 0 && K > 0, "ullsam_gemm: empty problem M=%d N=%d K=%d", M, N, K);
     const int esz = dtype == ULLSAM_DT_F32 ? 4 : 2;
@@ -2130,7 +2169,24 @@ static int gemm_impl(int dtype, const void* A, long lda, const void* W, long ldw
     }
     ULLSAM_CHECK(!w_panels || (dtype == ULLSAM_DT_BF16 && ((uintptr_t)w_panels & 1023) == 0 && N % 16 == 0 && K % 32 == 0),
                  "ullsam_gemm: K-panels are bf16 [N / 16][K / 32][16][32], 1 KiB aligned (N=%d K=%d)", N, K);
+    ULLSAM_CHECK(!a_panels || (dtype == ULLSAM_DT_BF16 && K % 32 == 0 && lda == K && ((uintptr_t)A & 1023) == 0),
+                 "ullsam_gemm: activation K-panels (A) are bf16 [ceil(M / 16)][K / 32][16][32], contiguous (lda == K), 1 KiB aligned (K=%d lda=%ld)", K, lda);
+    ULLSAM_CHECK(!out_panels || (dtype == ULLSAM_DT_BF16 && !out_f32 && act != 4 && (act == 3 ? N / 2 : N) % 32 == 0 && ldc == (act == 3 ? N / 2 : N) && ((uintptr_t)C & 1023) == 0),
+                 "ullsam_gemm: activation K-panels (C) are bf16 [ceil(M / 16)][N_out / 32][16][32], contiguous, 1 KiB aligned (N=%d ldc=%ld)", N, ldc);
     a.A = A; a.W = W; a.C = C; a.bias = bias; a.residual = residual; a.w_panels = w_panels;
+    a.a_panels = a_panels; a.out_panels = out_panels; a.plan = plan;
+    // Every route but the two ring kernels: the query's answer is no twice, and a launch that carries a panel flag is refused before anything is launched
+    // (a panel buffer is never read or written as row-major).
+    auto not_ring = [&](int& rc) -> bool {
+        if (plan) { plan[0] = plan[1] = 0; rc = 0; return true; }
+        if (a_panels || out_panels) {
+            ullsam_set_error("ullsam_gemm: activation K-panels refused: this launch (M=%d N=%d K=%d act=%d) does not reach a ring kernel -- ask the query first", M, N, K, act);
+            rc = -1;
+            return true;
+        }
+        return false;
+    };
+    int nr = 0;
     a.M = M; a.N = N; a.K = K;
     a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr;
     a.res_row_mod = res_row_mod; a.act = act; a.out_f32 = out_f32;
@@ -2155,7 +2211,7 @@ static int gemm_impl(int dtype, const void* A, long lda, const void* W, long ldw
     // (the forced variants select TILE kernels; a launch with the RMSNorm prologue exists in the skinny kernels only and goes there whatever is forced)
     if ((variant == 0 || norm) && (act != 4 || (M <= 4 && K % 2048 == 0)) && dtype == ULLSAM_DT_BF16 && M <= 8 && K % 512 == 0 && lda % 8 == 0 && ldw % 8 == 0 &&
         (size_t)(M <= 4 ? 4 : 8) * K * 2 <= 144 * 1024 && (act != 3 || N % 128 == 0))
-        return launch_gemm_skinny<false>(a, s);
+        return not_ring(nr) ? nr : launch_gemm_skinny<false>(a, s);
     ULLSAM_CHECK(!norm, "ullsam_gemm: the RMSNorm prologue exists in the decode-step kernels only (bf16, M <= 4, K <= 4096; got M=%d K=%d)", M, K);
     const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256);
     // 256-row tiles run one per CU: use them when the last round of tiles is >= 74 % full (measured crossover, tools/gemm_bench.py:
@@ -2176,6 +2232,7 @@ static int gemm_impl(int dtype, const void* A, long lda, const void* W, long ldw
         if (!ring_ok || (variant == 8 && act == 3)) { ullsam_set_error("ullsam_gemm: the ring kernels need bf16, K %% 64 == 0, K >= 128, no RoPE epilogue (256x320: no SwiGLU)"); return -1; }
         return variant == 6 ? launch_gemm_v6(a, s) : variant == 8 ? launch_gemm_v8(a, s) : launch_gemm_v9(a, s);
     }
+    if ((variant == 1 || variant == 3) && not_ring(nr)) return nr;
     if (variant == 1) return a.act == 4 ? (dtype == ULLSAM_DT_F32 ? launch_gemm<float, 1>(a, s) : launch_gemm<bf16, 1>(a, s))
                                         : (dtype == ULLSAM_DT_F32 ? launch_gemm<float>(a, s) : launch_gemm<bf16>(a, s));
     if (variant == 3) {
@@ -2189,6 +2246,7 @@ static int gemm_impl(int dtype, const void* A, long lda, const void* W, long ldw
     if (ring_ok && variant == 0 && (g_ring_splitk == 2 || (g_ring_splitk == 1 && split_ok))) {   // few tiles under a long sum: K ranges of the ring kernel side by side (launch_gemm_ring_splitk)
         int shape = 0;
         const int S = ring_splitk_plan(a, &shape);
+        if (S && not_ring(nr)) return nr;
         if (S) return shape == 8 ? launch_gemm_ring_splitk<8, 8, 5>(a, S, s) : shape == 9 ? launch_gemm_ring_splitk<9, 8, 4>(a, S, s) : launch_gemm_ring_splitk<8, 8, 4>(a, S, s);
     }
     if (ring_ok && M >= 1024 && N >= 256 && K >= 256) {
@@ -2200,6 +2258,7 @@ static int gemm_impl(int dtype, const void* A, long lda, const void* W, long ldw
         if (c272 <= 0.96 * c256) return launch_gemm_v9(a, s);
         if ((g_auto_mask & 1) && big && fill >= 0.74 && !v3_split) return launch_gemm_v6(a, s);
     }
+    if (not_ring(nr)) return nr;
     const bool v3 = big && (fill >= 0.74 || v3_split);
     if (v3) return dtype == ULLSAM_DT_F32 ? launch_gemm_v3<float>(a, s) : launch_gemm_v3<bf16>(a, s);   // fp32, the RoPE epilogue, bf16 shapes no ring takes
     if (a.act == 4) return dtype == ULLSAM_DT_F32 ? launch_gemm<float, 1>(a, s) : launch_gemm<bf16, 1>(a, s);
@@ -2325,4 +2384,51 @@ extern "C" int ullsam_gemm_qkv_rope_panels(int dtype, const void* A, long lda, c
     RopeEpilogue r{pos, cos_tab, sin_tab, q_out, k_cache, v_cache, S, KVH, G, cap, cache_pos0, tab_rows};
     const int N = KVH * (G + 2) * 128;
     return gemm_impl(dtype, A, lda, W, ldw, q_out, (long)KVH * G * 128, 0, bias, nullptr, 0, 0, 4, B * S, N, K, workspace, ws_bytes, stream, &r, nullptr, w_panels);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Activation K-panels (packing.pack_activation_panels; gemm_ring8p.h has the layout): the ring kernels read a bf16 activation that its PRODUCER wrote
+// as [ceil(M / 16)][K / 32][16][32] (a_panels) and write their own 2-byte output so for the next GEMM (out_panels).  A caller asks the query for the launch
+// it is about to make and sets a flag only where the answer is yes; a flag on a launch that does not take it is an error before anything is launched.
+// ---------------------------------------------------------------------------------------------------------------
+// ullsam_gemm_panels (w_panels may be NULL) with the two flags.
+extern "C" int ullsam_gemm_act_panels(int dtype, const void* A, long lda, const void* W, long ldw, const void* w_panels, void* C, long ldc, int out_f32,
+                                      const float* bias, const float* residual, long ldr, int res_row_mod, int act, int M, int N,
+                                      int K, void* workspace, long ws_bytes, int a_panels, int out_panels, void* stream) {
+    ULLSAM_CHECK(act != 4, "ullsam_gemm_act_panels: act 4 is ullsam_gemm_qkv_rope_act_panels");
+    return gemm_impl(dtype, A, lda, W, ldw, C, ldc, out_f32, bias, residual, ldr, res_row_mod, act, M, N, K, workspace, ws_bytes, stream, nullptr, nullptr, w_panels,
+                     a_panels != 0, out_panels != 0);
+}
+// ullsam_gemm_qkv_rope_panels (w_panels may be NULL) reading A as panels; q / k / v stay row-major.
+extern "C" int ullsam_gemm_qkv_rope_act_panels(int dtype, const void* A, long lda, const void* W, long ldw, const void* w_panels, const float* bias, int B, int S,
+                                               int K, int KVH, int G, const int* pos, const float* cos_tab, const float* sin_tab, int tab_rows, void* q_out,
+                                               void* k_cache, void* v_cache, int cap, int cache_pos0, void* workspace, long ws_bytes, int a_panels, void* stream) {
+    ULLSAM_CHECK(B > 0 && S > 0 && KVH > 0 && G > 0 && tab_rows > 0, "ullsam_gemm_qkv_rope_act_panels: bad dims");
+    ULLSAM_CHECK(cache_pos0 + S <= cap, "ullsam_gemm_qkv_rope_act_panels: cache overflow (%d + %d > %d)", cache_pos0, S, cap);
+    ULLSAM_CHECK(((uintptr_t)q_out & 15) == 0 && ((uintptr_t)k_cache & 15) == 0 && ((uintptr_t)v_cache & 15) == 0, "ullsam_gemm_qkv_rope_act_panels: 16-byte aligned outputs needed");
+    RopeEpilogue r{pos, cos_tab, sin_tab, q_out, k_cache, v_cache, S, KVH, G, cap, cache_pos0, tab_rows};
+    const int N = KVH * (G + 2) * 128;
+    return gemm_impl(dtype, A, lda, W, ldw, q_out, (long)KVH * G * 128, 0, bias, nullptr, 0, 0, 4, B * S, N, K, workspace, ws_bytes, stream, &r, nullptr, w_panels, a_panels != 0, 0);
+}
+// Would this launch read A as panels / could it write C as panels?  Runs the dispatch of the launch itself (gemm_impl with a plan instead of a stream), so the
+// two cannot disagree.  The launch is described as the callers make it: contiguous operands (lda = ldw = K, ldc = N_out), act as for ullsam_gemm (4 = the wqkv +
+// RoPE launch, N = KVH (G + 2) 128), has_bias / has_residual, ws_bytes of workspace, `aligned` = A and C on 1 KiB boundaries (ops.empty_activation_panels) and
+// bias / residual on 16-byte ones.  Launches nothing.
+extern "C" int ullsam_gemm_act_panels_query(int dtype, int M, int N, int K, int act, int out_f32, int has_bias, int has_residual, int aligned, long ws_bytes,
+                                            int* reads_a_panels, int* writes_c_panels) {
+    ULLSAM_CHECK(reads_a_panels && writes_c_panels, "ullsam_gemm_act_panels_query: null answer");
+    *reads_a_panels = *writes_c_panels = 0;
+    char* const base = reinterpret_cast<char*>((uintptr_t)1 << 30);   // never dereferenced
+    char* const op = aligned ? base : base + 16;
+    const float* fp = reinterpret_cast<const float*>(base);
+    const int a4 = act & 255;
+    const int n_out = a4 == 3 ? N / 2 : N;
+    RopeEpilogue r{reinterpret_cast<const int*>(base), fp, fp, base, base, base, M, 1, N / 128 - 2, M, 0, M};
+    ULLSAM_CHECK(a4 != 4 || (N % 128 == 0 && N >= 384), "ullsam_gemm_act_panels_query: the RoPE launch has N = KVH (G + 2) 128, got %d", N);
+    int plan[2] = {0, 0};
+    const int rc = gemm_impl(dtype, op, K, base, K, op, a4 == 4 ? N - 256 : n_out, out_f32, has_bias ? fp : nullptr, has_residual ? fp : nullptr, n_out, 0, act, M, N, K,
+                             ws_bytes > 0 ? base : nullptr, ws_bytes, nullptr, a4 == 4 ? &r : nullptr, nullptr, nullptr, 0, 0, plan);
+    if (rc != 0) return rc;
+    *reads_a_panels = plan[0]; *writes_c_panels = plan[1];
+    return 0;
 }

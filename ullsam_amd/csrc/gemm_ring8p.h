@@ -124,19 +124,27 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
     const int wp_shift = panels ? 4 : 0;
     const unsigned int wp_mask = panels ? 15u : 0u, wp_block = panels ? (unsigned int)p.K * 32u : (unsigned int)(p.ldw * 2);
     const unsigned int kst = __builtin_amdgcn_readfirstlane(panels ? 1024u : 64u);   // bytes of W from one stage to the next
+    // The activation as K-panels (p.a_panels, packing.pack_activation_panels: the same cell, [ceil(M / 16)][K / 32][16 rows][32 k]) likewise: tile row R at
+    // (R / 16) (K / 32) 1024 + (R % 16) 64, a stage further 1024 bytes further (a scalar like W's, where the row-major step is 64), a_tile unchanged (BM % 16 == 0, lda == K).
+    // The descriptor spans the padded rows: rows M .. the next multiple of 16 exist in the buffer, are never written, and feed accumulator rows >= M only; whole
+    // 16-row blocks past them are out of range as rows past M are in the row-major form.
+    const bool a_pan = p.a_panels != 0;
+    const int ap_shift = a_pan ? 4 : 0;
+    const unsigned int ap_mask = a_pan ? 15u : 0u, ap_block = a_pan ? (unsigned int)p.K * 32u : (unsigned int)(p.lda * 2);
+    const unsigned int akst = __builtin_amdgcn_readfirstlane(a_pan ? 1024u : 64u);   // bytes of A from one stage to the next
     unsigned int a_off[3], b_off[3];
     auto set_offsets = [&](int ln) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const int row = (wave + 8 * i) * 16 + (ln >> 2);
             const int c = (ln & 3) ^ ((row >> 2) & 2);
-            a_off[i] = (unsigned int)row * (unsigned int)(p.lda * 2) + (c << 4);
+            a_off[i] = ((unsigned int)row >> ap_shift) * ap_block + ((unsigned int)row & ap_mask) * 64u + (c << 4);
             const unsigned int wr = (unsigned int)w_row(row);
             b_off[i] = (wr >> wp_shift) * wp_block + (wr & wp_mask) * 64u + (c << 4);
         }
     };
     set_offsets(lane);
-    const u32x4 a_desc = raw_desc(p.A, (unsigned int)(((size_t)(p.M - 1) * p.lda + p.K) * 2));
+    const u32x4 a_desc = raw_desc(p.A, a_pan ? (unsigned int)((size_t)((p.M + 15) & ~15) * p.K * 2) : (unsigned int)(((size_t)(p.M - 1) * p.lda + p.K) * 2));
     const u32x4 b_desc = raw_desc(panels ? p.w_panels : p.W, (unsigned int)(((size_t)(p.N - 1) * p.ldw + p.K) * 2));
     const unsigned int a_tile = (unsigned int)(p.lda * 2) * BM, b_tile = (unsigned int)(p.ldw * 2) * BN;   // bytes from one tile row / column to the next
     const int st1 = p.K >> 5;  // stages (32-deep k-steps) per tile, a multiple of 4, at least 12
@@ -168,7 +176,7 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
     tile_of(blockIdx.x, tm0, tn0);
     bias_dma(tn0 * BN, 0);
     request_stage(tm0 * a_tile, tn0 * b_tile, 0);
-    request_stage(tm0 * a_tile + 64, tn0 * b_tile + kst, 1);
+    request_stage(tm0 * a_tile + akst, tn0 * b_tile + kst, 1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (grp == 1) __builtin_amdgcn_s_barrier();
@@ -178,6 +186,7 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
         constexpr int MIW = decltype(MIW_c)::value;
         constexpr int DG = 2;   // request distance: stages between a request and its use (the one-tile kernel's)
         const unsigned int kstep[4] = {kst * DG, kst * (DG + 1), kst * (DG + 2), kst * (DG + 3)};   // W's byte offset of the stage requested from ring slot J, relative to the trip's scalar offset
+        const unsigned int akstep[4] = {akst * DG, akst * (DG + 1), akst * (DG + 2), akst * (DG + 3)};   // ... and A's (64 bytes per stage row-major, 1024 as panels)
         const int row_w = decltype(ROWW_c)::value >= 0 ? decltype(ROWW_c)::value : wm * (MI0 * 16);   // first tile row of this wave's row (run time when both rows share one instantiation)
         f32x4 acc[MIW][NTW];
 #pragma unroll
@@ -198,14 +207,14 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
         // wait), barrier, matrix slot, barrier.  The K loop is unrolled by the ring's four slots, so that the slot of a stage (read slot J, request slot
         // (J + 2) & 3) and with it every LDS address -- the M0 value of a request, the offsets of the reads -- is a compile-time constant: a request is
         // THREE instructions (s_add_i32 m0, base, imm / s_nop / buffer_load ... offset:imm lds) where the one-tile kernel spends six plus the slot arithmetic
-        // (its load slot is the critical path of a stage and carries ~35 scalar instructions per stage; here ~10).  The k offset of a request rides in the
-        // instruction's immediate (64 bytes per stage, relative to the trip's scalar offset), so the scalar offsets move once per trip.
-        // Every stage requests, at so_a / so_b + 64 (J + 2).
+        // (its load slot is the critical path of a stage and carries ~35 scalar instructions per stage; here ~10).  The k offset of a request is one
+        // scalar add per operand (akstep[J] / kstep[J]: 64 bytes per stage row-major, 1024 as panels, relative to the trip's scalar offset), so the scalar offsets move
+        // once per trip.  Every stage requests, at so_a / so_b + step (J + 2).
         auto stage = [&](auto J_c, unsigned int so_a, unsigned int so_b, auto NA_c, auto NB_c) __attribute__((always_inline)) {
             constexpr int J = decltype(J_c)::value;
             constexpr int NA = decltype(NA_c)::value, NB = decltype(NB_c)::value;
-            constexpr int RS = (J + DG) & 3, KOFF = 64 * (J + DG);
-            const unsigned int rq_a = so_a + KOFF, rq_b = so_b + kstep[J];   // (two scalar adds per stage; W's step is a scalar: 64 bytes row-major, 1024 as panels)
+            constexpr int RS = (J + DG) & 3;
+            const unsigned int rq_a = so_a + akstep[J], rq_b = so_b + kstep[J];   // (two scalar adds per stage; the steps are scalars: 64 bytes row-major, 1024 as panels)
             // this stage's read bases: the wave's per-lane bases (rd_a / rd_b, below) + the slot's offset, ONE add each, pinned here -- left to itself
             // hipcc keeps a base register per slot and (where it cannot see that the swizzle depends on the lane only) per fragment: 20 registers and
             // spills in the 256x320 instantiation; the fragments then sit at immediate offsets of 1 KiB
@@ -264,16 +273,16 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
         auto run_tile = [&](auto NA_c, auto NB_c, unsigned int sa, unsigned int sb, unsigned int san, unsigned int sbn) __attribute__((always_inline)) {
             using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
             const int ntrip = st1 >> 2;
-            const unsigned int ktrip = 4u * kst;
+            const unsigned int ktrip = 4u * kst, atrip = 4u * akst;
             unsigned int ra = sa, rb = sb;
             for (int t = 0; t < ntrip; ++t) {
                 const bool last = t == ntrip - 1;   // (no stamps inside a stage: inside the one loop body they cost the loop its shape -- 3 x the cycles per stage; the tile-level stamps stay)
-                const unsigned int ha = last ? san - 256u : ra, hb = last ? sbn - ktrip : rb;   // stages 2 / 3 of the last trip request stages 0 / 1 of the next tile: (san - 256) + 64 (J + 2)
+                const unsigned int ha = last ? san - atrip : ra, hb = last ? sbn - ktrip : rb;   // stages 2 / 3 of the last trip request stages 0 / 1 of the next tile: (san - 4 step) + step (J + 2)
                 stage(I0{}, ra, rb, NA_c, NB_c);
                 stage(I1{}, ra, rb, NA_c, NB_c);
                 stage(I2{}, ha, hb, NA_c, NB_c);
                 stage(I3{}, ha, hb, NA_c, NB_c);
-                ra += 256; rb += ktrip;
+                ra += atrip; rb += ktrip;
             }
         };
 
@@ -327,6 +336,13 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
                 const int row0 = m0 + row_w + mm;
                 const int rowp = row0 & ~1;
                 auto gst = [&](void* ptr, u32x4 vv) __attribute__((always_inline)) { *reinterpret_cast<u32x4*>(ptr) = vv; };
+                // C as activation K-panels (p.out_panels; gemm_ring8_kernel's epilogue has the argument): o_r16 / o_r1 = elements from a row to the row 16 / 1 below it
+                const bool o_pan = p.out_panels != 0;
+                const size_t o_cells = (size_t)((p.act == 3 ? p.N >> 1 : p.N) >> 5);
+                const size_t o_r16 = o_pan ? o_cells * 512 : (size_t)16 * p.ldc, o_r1 = o_pan ? (size_t)32 : (size_t)p.ldc;
+                auto o_at = [&](int row, int col) __attribute__((always_inline)) -> size_t {
+                    return o_pan ? ((size_t)(row >> 4) * o_cells + (size_t)(col >> 5)) * 512 + (size_t)((row & 15) * 32 + (col & 31)) : (size_t)row * p.ldc + col;
+                };
                 if constexpr (EMODE == 1) {
                     // wqkv + RoPE + KV-cache append (modeling_internlm2.py:359-388, 233-247): see gemm_ring8_kernel
                     const int slot = (n0 >> 7) + (wn >> 1), d = 32 * (wn & 1) + 8 * g4;
@@ -382,9 +398,9 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
                 } else if (!p.out_f32 && p.act != 3) {
                     // bf16 (+bias, +GELU / ReLU)
                     const int colb = n0 + wn * WW + (odd ? 32 : 0) + 8 * g4;
-                    T* cp = reinterpret_cast<T*>(p.C) + (size_t)rowp * p.ldc + colb;
+                    T* cp = reinterpret_cast<T*>(p.C) + o_at(rowp, colb);
                     const int col5 = n0 + wn * WW + 64 + 4 * g4;
-                    T* cp5 = reinterpret_cast<T*>(p.C) + (size_t)row0 * p.ldc + col5;
+                    T* cp5 = reinterpret_cast<T*>(p.C) + o_at(row0, col5);
                     auto drain = [&](auto ACT) __attribute__((always_inline)) {
                         uint2 w5 = make_uint2(0u, 0u);
                         auto actf = [&](float x) __attribute__((always_inline)) {
@@ -405,8 +421,8 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
                             u32x4 s0, s1;
                             pair_swap((u32x4){o[0], o[1], o[2], o[3]}, (u32x4){o[4], o[5], o[6], o[7]}, odd, s0, s1);
                             if (rowp + 16 * i < p.M) {
-                                gst(cp + (size_t)(16 * i) * p.ldc, s0);
-                                gst(cp + (size_t)(16 * i + 1) * p.ldc, s1);
+                                gst(cp + i * o_r16, s0);
+                                gst(cp + i * o_r16 + o_r1, s1);
                             }
                             if constexpr (NTW == 5) {
                                 uint2 w;
@@ -418,12 +434,12 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
                                         const auto ry = __builtin_amdgcn_permlane16_swap(w5.y, w.y, false, false);
                                         const int r5 = row0 + 16 * (i - 1 + (g4 & 1));
                                         if (r5 < p.M)
-                                            gst(reinterpret_cast<T*>(p.C) + (size_t)r5 * p.ldc + (n0 + wn * WW + 64 + 8 * (g4 >> 1)), (u32x4){rx[0], ry[0], rx[1], ry[1]});
+                                            gst(reinterpret_cast<T*>(p.C) + o_at(r5, n0 + wn * WW + 64 + 8 * (g4 >> 1)), (u32x4){rx[0], ry[0], rx[1], ry[1]});
                                     } else {
                                         w5 = w;
                                     }
                                 } else {
-                                    if (row0 + 16 * i < p.M) *reinterpret_cast<uint2*>(cp5 + (size_t)(16 * i) * p.ldc) = w;
+                                    if (row0 + 16 * i < p.M) *reinterpret_cast<uint2*>(cp5 + i * o_r16) = w;
                                 }
                             }
                         }
@@ -433,7 +449,7 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
                     else drain(std::integral_constant<int, 0>{});
                 } else if (NTW == 4 && !p.out_f32 && p.act == 3) {
                     // SwiGLU (modeling_internlm2.py:261-264)
-                    T* cp = reinterpret_cast<T*>(p.C) + (size_t)row0 * p.ldc + (n0 >> 1) + (wn >> 1) * 64 + (wn & 1) * 32 + 8 * g4;
+                    T* cp = reinterpret_cast<T*>(p.C) + o_at(row0, (n0 >> 1) + (wn >> 1) * 64 + (wn & 1) * 32 + 8 * g4);
     #pragma unroll
                     for (int i = 0; i < MIW; ++i) {
                         border_sync(i, 1);
@@ -444,7 +460,7 @@ __global__ __launch_bounds__(512) void gemm_ring8p_kernel(GemmArgs p) {
                             const float u0 = acc[i][2 + (q >> 1)][2 * (q & 1)], u1 = acc[i][2 + (q >> 1)][2 * (q & 1) + 1];
                             o[q] = pack_bf16x2(g0 * __builtin_amdgcn_rcpf(1.0f + __expf(-g0)) * u0, g1 * __builtin_amdgcn_rcpf(1.0f + __expf(-g1)) * u1);
                         }
-                        if (row0 + 16 * i < p.M) gst(cp + (size_t)(16 * i) * p.ldc, (u32x4){o[0], o[1], o[2], o[3]});
+                        if (row0 + 16 * i < p.M) gst(cp + i * o_r16, (u32x4){o[0], o[1], o[2], o[3]});
                     }
                 } else {
                     // fp32 residual stream: C = acc + bias + residual[row (mod res_row_mod)]

@@ -22,7 +22,16 @@ struct NormArgs {
     int act;  // 0 none, 1 gelu
     const float* post_scale;  // device scalar or null
     const float* post_shift;  // device scalar or null
+    // bf16 output as the ring GEMM's activation K-panels (packing.pack_activation_panels: [ceil(rows / 16)][D / 32][16 rows][32 k], D % 32 == 0, out_stride == D):
+    // only the address of each 4-element store changes -- element (row, k) sits at ((row / 16) (D / 32) + k / 32) 512 + (row % 16) 32 + k % 32
+    int out_panels;
 };
+// where float4 group `idx` of `row` goes: y (the row's base, row-major) + 4 idx, or its place in the panels
+template <typename TO>
+__device__ __forceinline__ TO* norm_dst(const NormArgs& p, TO* y, long row, int idx) {
+    if (!p.out_panels) return y + idx * 4;
+    return reinterpret_cast<TO*>(p.out) + ((row >> 4) * (p.D >> 5) + (idx >> 3)) * 512 + ((int)(row & 15) * 32 + (idx & 7) * 4);
+}
 
 template <typename TI, typename TO, int MAXV>
 __global__ __launch_bounds__(256) void norm_kernel(NormArgs p) {
@@ -75,7 +84,7 @@ __global__ __launch_bounds__(256) void norm_kernel(NormArgs p) {
             }
             if (post) { o.x = o.x * ps + pb; o.y = o.y * ps + pb; o.z = o.z * ps + pb; o.w = o.w * ps + pb; }
             if (p.act == 1) { o.x = gelu_erf(o.x); o.y = gelu_erf(o.y); o.z = gelu_erf(o.z); o.w = gelu_erf(o.w); }
-            store4(y + idx * 4, o);
+            store4(norm_dst(p, y, row, idx), o);
         }
     }
 }
@@ -89,7 +98,12 @@ __global__ __launch_bounds__(256) void norm_block_kernel(NormArgs p) {
     constexpr int TPR = WPR * 64;                 // threads per row
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int sub = wv / WPR, t = tid - sub * TPR;  // row slot inside the workgroup, thread index inside the row
-    const long row = (long)blockIdx.x * (4 / WPR) + sub;
+    // Panels: a 128-byte line of a cell holds the same 32 k of rows 2 j and 2 j + 1.  Workgroups go round the eight XCDs in dispatch order, so neighbouring rows would
+    // write the two halves of every line into two different L2s (byte-masked partial lines on their way out: +4 us on [4324, 4096]); inside each group of 16
+    // workgroups the rows are dealt so that workgroups s and s + 8 -- the same XCD, dispatched together -- own such a pair.  (The grid is rounded up to 16 for it.)
+    long blk = blockIdx.x;
+    if (p.out_panels) { const int s16 = (int)(blk & 15); blk = (blk & ~15l) | (long)((4 / WPR == 1) ? 2 * (s16 & 7) + (s16 >> 3) : s16); }
+    const long row = blk * (4 / WPR) + sub;
     const bool live = row < p.rows;
     const TI* x = reinterpret_cast<const TI*>(p.in) + (live ? row : 0) * p.in_stride;
     TO* y = reinterpret_cast<TO*>(p.out) + (live ? row : 0) * p.out_stride;
@@ -147,7 +161,7 @@ __global__ __launch_bounds__(256) void norm_block_kernel(NormArgs p) {
             }
             if (post) { o.x = o.x * ps + pb; o.y = o.y * ps + pb; o.z = o.z * ps + pb; o.w = o.w * ps + pb; }
             if (p.act == 1) { o.x = gelu_erf(o.x); o.y = gelu_erf(o.y); o.z = gelu_erf(o.z); o.w = gelu_erf(o.w); }
-            store4(y + idx * 4, o);
+            store4(norm_dst(p, y, row, idx), o);
         }
     }
 }
@@ -203,6 +217,7 @@ static int launch_norm(const NormArgs& a, hipStream_t s) {
     const dim3 grid((unsigned)((a.rows + 3) / 4)), block(256);
     const int nv = a.D / 4;
     if (nv <= 16 && a.rows >= 4096) {
+        ULLSAM_CHECK(!a.out_panels, "ullsam_norm_panels: D=%d rows go to the narrow kernel, which writes row-major only", a.D);
         norm_narrow_kernel<TI, TO><<<dim3((unsigned)((a.rows + 15) / 16)), block, 0, s>>>(a);
         ULLSAM_LAUNCH_CHECK();
         return 0;
@@ -211,7 +226,7 @@ static int launch_norm(const NormArgs& a, hipStream_t s) {
     // (4.0 TB/s) against 37.9 us with a wave per row; at 1280 elements (ViT LayerNorm) the wave-per-row kernel stays ahead (33.6 vs 37.7)
     // ... and so does a handful of long rows (the decode step: 4 rows x 4096 took 14.6 us with one wave per row)
     if (g_norm_lds == 0 && (a.rows >= 1024 || a.rows <= 64) && nv >= 512) {
-        const dim3 g((unsigned)a.rows);
+        const dim3 g((unsigned)(a.out_panels ? (a.rows + 15) / 16 * 16 : a.rows));
         if (nv <= 512) norm_block_kernel<TI, TO, 2><<<g, block, 0, s>>>(a);
         else norm_block_kernel<TI, TO, 4><<<g, block, 0, s>>>(a);
         ULLSAM_LAUNCH_CHECK();
@@ -282,13 +297,28 @@ extern "C" int ullsam_norm(const void* in, int in_dtype, long in_stride, void* o
     ULLSAM_CHECK(rows >= 0, "ullsam_norm: bad rows");
     if (rows == 0) return 0;
     ULLSAM_CHECK(in_stride % 4 == 0 && out_stride % 4 == 0, "ullsam_norm: strides must be multiples of 4 elements");
-    NormArgs a{in, out, w, rms ? nullptr : b, rows, D, in_stride, out_stride, eps, rms, act, post_scale, post_shift};
+    NormArgs a{in, out, w, rms ? nullptr : b, rows, D, in_stride, out_stride, eps, rms, act, post_scale, post_shift, 0};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (in_dtype == 0 && out_dtype == 0) return launch_norm<float, float>(a, s);
     if (in_dtype == 0 && out_dtype == 1) return launch_norm<float, bf16>(a, s);
     if (in_dtype == 1 && out_dtype == 1) return launch_norm<bf16, bf16>(a, s);
     if (in_dtype == 1 && out_dtype == 0) return launch_norm<bf16, float>(a, s);
     ULLSAM_CHECK(false, "ullsam_norm: bad dtypes %d %d", in_dtype, out_dtype);
+}
+
+// ullsam_norm with a bf16 output written as activation K-panels (out_panels != 0): `out` is the 1 KiB-aligned buffer of ceil(rows / 16) * 16 rows of D elements
+// (its rows past `rows` are not written), D % 32 == 0.  Same arithmetic, same order of the reductions, same values: only where each goes.
+extern "C" int ullsam_norm_panels(const void* in, int in_dtype, long in_stride, void* out, const float* w, const float* b, long rows, int D, float eps,
+                                  int rms, int act, const float* post_scale, const float* post_shift, int out_panels, void* stream) {
+    ULLSAM_CHECK(D % 4 == 0 && D > 0 && D <= 4096, "ullsam_norm_panels: D=%d must be a multiple of 4 and <= 4096", D);
+    ULLSAM_CHECK(rows >= 0 && in_stride % 4 == 0, "ullsam_norm_panels: bad rows / input stride");
+    ULLSAM_CHECK(!out_panels || (D % 32 == 0 && ((uintptr_t)out & 1023) == 0), "ullsam_norm_panels: panels need D %% 32 == 0 and a 1 KiB aligned output (D=%d)", D);
+    if (rows == 0) return 0;
+    NormArgs a{in, out, w, rms ? nullptr : b, rows, D, in_stride, (long)D, eps, rms, act, post_scale, post_shift, out_panels != 0};
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (in_dtype == 0) return launch_norm<float, bf16>(a, s);
+    if (in_dtype == 1) return launch_norm<bf16, bf16>(a, s);
+    ULLSAM_CHECK(false, "ullsam_norm_panels: bad input dtype %d", in_dtype);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -148,14 +148,17 @@ class ImageEncoderViT(Packed):
         pos = None if self.pos_embed is None else self.f32("pos", self.pos_embed).reshape(N, D)
         xres = ops.gemm(cols, wp, None if pe.bias is None else self.f32("patch_b", pe.bias), residual=pos, res_row_mod=N, out_f32=True)
         fp8 = bool(self.fp8_linears) and dt == torch.bfloat16 and D % 128 == 0
+        M, hp = xres.shape[0], False   # hp: this block's lin1 output travels to lin2 as K-panels
         for bi, blk in enumerate(self.blocks):
             at = blk.attn
             if fp8:
                 q8, sa = ops.rows_fp8(xres, *blk.norm1.wb(), blk.norm1.eps)
                 qkv = ops.gemm_fp8(q8, sa, *at.qkv.w8(), at.qkv.b())
             else:
-                xn = ops.norm(xres, *blk.norm1.wb(), blk.norm1.eps, dt)
-                qkv = ops.gemm(xn, at.qkv.w(dt), at.qkv.b(), w_panels=at.qkv.wp(dt, xn.shape[0]))
+                # (the norm writes xn as the K-panels the qkv launch reads, where that launch reads panels: ops.activation_panels_plan)
+                ap, _ = ops.activation_panels_plan(M, 3 * D, D, dt, bias=at.qkv.b() is not None)
+                xn = ops.norm(xres, *blk.norm1.wb(), blk.norm1.eps, dt, out_panels=ap)
+                qkv = ops.gemm(xn, at.qkv.w(dt), at.qkv.b(), w_panels=at.qkv.wp(dt, M), a_panels=ap, m=M)
             qb = at.qkv.bias if at.qkv.bias is not None else torch.zeros(3 * D, device=x.device)
             n_rel = blk.window_size if blk.window_size > 0 else g
             att = ops.vit_attention(qkv, at.rel_table("rh", at.rel_pos_h, n_rel, dt), at.rel_table("rw", at.rel_pos_w, n_rel, dt), at.cdt("qb", qb, dt),
@@ -165,9 +168,13 @@ class ImageEncoderViT(Packed):
                 q8, sa = ops.rows_fp8(xres, *blk.norm2.wb(), blk.norm2.eps)
                 h = ops.gemm_fp8(q8, sa, *blk.mlp.lin1.w8(), blk.mlp.lin1.b(), act=blk.mlp.act_code)
             else:
-                xn = ops.norm(xres, *blk.norm2.wb(), blk.norm2.eps, dt)
-                h = ops.gemm(xn, blk.mlp.lin1.w(dt), blk.mlp.lin1.b(), act=blk.mlp.act_code, w_panels=blk.mlp.lin1.wp(dt, xn.shape[0]))
-            ops.gemm(h, blk.mlp.lin2.w(dt), blk.mlp.lin2.b(), residual=xres, out_f32=True, out=xres, w_panels=blk.mlp.lin2.wp(dt, h.shape[0]))
+                # norm -> lin1 -> lin2 on K-panels: each producer writes what the next launch reads, where both launches agree
+                w1, w2 = blk.mlp.lin1.w(dt), blk.mlp.lin2.w(dt)
+                ap, cp = ops.activation_panels_plan(M, w1.shape[0], D, dt, act=blk.mlp.act_code, bias=blk.mlp.lin1.b() is not None)
+                hp = cp and ops.activation_panels_plan(M, D, w2.shape[1], dt, out_f32=True, bias=blk.mlp.lin2.b() is not None, residual=True)[0]
+                xn = ops.norm(xres, *blk.norm2.wb(), blk.norm2.eps, dt, out_panels=ap)
+                h = ops.gemm(xn, w1, blk.mlp.lin1.b(), act=blk.mlp.act_code, w_panels=blk.mlp.lin1.wp(dt, M), a_panels=ap, out_panels=hp, m=M)
+            ops.gemm(h, blk.mlp.lin2.w(dt), blk.mlp.lin2.b(), residual=xres, out_f32=True, out=xres, w_panels=blk.mlp.lin2.wp(dt, M), a_panels=hp, m=M)
             if self.stage_probe is not None:
                 self.stage_probe(bi, xres)
         n0, n1, n2, n3 = self.neck[0], self.neck[1], self.neck[2], self.neck[3]

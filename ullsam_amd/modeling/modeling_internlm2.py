@@ -201,6 +201,7 @@ class InternLM2Model(Packed):
         fused = S == 1 and cache is not None and hd == 128 and ops.decode_fusable(B, cfg.hidden_size, dt) and self.fuse_decode
         w8 = bool(getattr(self, "fp8_decode", False)) and fused and x.is_cuda   # weight-only e4m3 streams; a wo / w2 whose K the kernels decline stays bf16
         w8_wo, w8_w2 = w8 and ops.decode_w8_ok(B, H * hd), w8 and ops.decode_w8_ok(B, cfg.intermediate_size)
+        hp = False   # this layer's w13 output travels to w2 as K-panels
         for li, layer in enumerate(self.layers):
             if collect is not None:
                 collect.append(x.reshape(B, S, -1).to(dt))
@@ -213,11 +214,14 @@ class InternLM2Model(Packed):
                 q = ops.decode_qkv_rope(x, layer.attention_norm.w(), layer.attention_norm.variance_epsilon, at.wqkv.w(dt), at.wqkv.b(), kc, vc,
                                         pos, cos, sin, B, KVH, G, past)
             else:
-                xn = ops.norm(x, layer.attention_norm.w(), None, layer.attention_norm.variance_epsilon, dt, rms=True)
-                if hd == 128 and S > 8:   # prefill: head split + RoPE + KV append in the wqkv GEMM's epilogue (no qkv round trip)
-                    q = ops.gemm_qkv_rope(xn, at.wqkv.w(dt), at.wqkv.b(), kc, vc, pos, cos, sin, B, S, KVH, G, past, w_panels=at.wqkv.wp(dt, B * S))
+                # (the norm writes xn as the K-panels the wqkv launch reads, where that launch reads panels: ops.activation_panels_plan)
+                wq, rope_ep = at.wqkv.w(dt), hd == 128 and S > 8
+                ap, _ = ops.activation_panels_plan(B * S, wq.shape[0], wq.shape[1], dt, bias=at.wqkv.b() is not None, rope=rope_ep)
+                xn = ops.norm(x, layer.attention_norm.w(), None, layer.attention_norm.variance_epsilon, dt, rms=True, out_panels=ap)
+                if rope_ep:   # prefill: head split + RoPE + KV append in the wqkv GEMM's epilogue (no qkv round trip)
+                    q = ops.gemm_qkv_rope(xn, wq, at.wqkv.b(), kc, vc, pos, cos, sin, B, S, KVH, G, past, w_panels=at.wqkv.wp(dt, B * S), a_panels=ap)
                 else:
-                    qkv = ops.gemm(xn, at.wqkv.w(dt), at.wqkv.b(), w_panels=at.wqkv.wp(dt, B * S))
+                    qkv = ops.gemm(xn, wq, at.wqkv.b(), w_panels=at.wqkv.wp(dt, B * S), a_panels=ap, m=B * S)
                     q = ops.rope_split(qkv, kc, vc, pos, cos, sin, B, S, KVH, G, hd, past)
             if S > 1:
                 a = ops.causal_attention(q, kc, vc, key_mask, B, H, KVH, hd, S, Sk, past)
@@ -236,12 +240,16 @@ class InternLM2Model(Packed):
             elif fused:
                 hmid = ops.gemm_rmsnorm(x, layer.ffn_norm.w(), layer.ffn_norm.variance_epsilon, ff.w13(dt), act=ops.ACT_SWIGLU)
             else:
-                xn = ops.norm(x, layer.ffn_norm.w(), None, layer.ffn_norm.variance_epsilon, dt, rms=True)
-                hmid = ops.gemm(xn, ff.w13(dt), act=ops.ACT_SWIGLU, w_panels=ff.w13p(dt, B * S))
+                # norm -> w13 -> w2 on K-panels: each producer writes what the next launch reads, where both launches agree (ops.activation_panels_plan)
+                w13, w2 = ff.w13(dt), ff.w2.w(dt)
+                ap, cp = ops.activation_panels_plan(B * S, w13.shape[0], w13.shape[1], dt, act=ops.ACT_SWIGLU)
+                hp = cp and not w8_w2 and ops.activation_panels_plan(B * S, w2.shape[0], w2.shape[1], dt, out_f32=True, residual=True)[0]
+                xn = ops.norm(x, layer.ffn_norm.w(), None, layer.ffn_norm.variance_epsilon, dt, rms=True, out_panels=ap)
+                hmid = ops.gemm(xn, w13, act=ops.ACT_SWIGLU, w_panels=ff.w13p(dt, B * S), a_panels=ap, out_panels=hp, m=B * S)
             if w8_w2:
                 ops.gemm_w8(hmid, *ff.w2.w8d(), None, residual=x, out_f32=True, out=x)
             else:
-                ops.gemm(hmid, ff.w2.w(dt), None, residual=x, out_f32=True, out=x, w_panels=ff.w2.wp(dt, B * S))
+                ops.gemm(hmid, ff.w2.w(dt), None, residual=x, out_f32=True, out=x, w_panels=ff.w2.wp(dt, B * S), a_panels=hp, m=B * S)
             if self.stage_probe is not None:
                 self.stage_probe(li, x)
         if cache is not None:

@@ -68,6 +68,40 @@ def ring_panels_wanted(M: int, N: int, K: int, dtype: torch.dtype) -> bool:
     return _RING_PANELS and dtype == torch.bfloat16 and M >= 1024 and K >= 256 and K % 64 == 0 and (N % 256 == 0 or N % 320 == 0)
 
 
+# Activations as K-panels (packing.pack_activation_panels, csrc/gemm_ring8p.h): a bf16 activation that one ring GEMM reads is written in the panel layout by the
+# kernel that produces it (a norm, or the GELU / SwiGLU epilogue of the GEMM before), so the consumer's LDS-DMA requests read whole lines.  No copy, no extra pass:
+# the only memory cost is up to 15 padding rows per buffer.  ULLSAM_ACTIVATION_PANELS=0 -- or set_activation_panels(False) -- is the off switch: every launch
+# then runs exactly as without the layout.  Same results either way, bit for bit.
+_ACT_PANELS = os.environ.get("ULLSAM_ACTIVATION_PANELS", "1") != "0"
+
+
+def set_activation_panels(on: bool) -> None:
+    """Process-wide: producers write and ring GEMMs read activations as K-panels where activation_panels_plan says so (default), or never."""
+    global _ACT_PANELS
+    _ACT_PANELS = bool(on)
+    _lib.call("ullsam_set_gemm_tuning", 5, 1 if on else 0)
+
+
+def activation_panels_plan(M: int, N: int, K: int, dtype: torch.dtype, act: int = ACT_NONE, out_f32: bool = False, bias: bool = False,
+                           residual: bool = False, rope: bool = False):
+    """(reads A as panels, can write C as panels) for the launch gemm() / gemm_qkv_rope() (rope=True) would make with operands from empty_activation_panels:
+    the answer of the library's own dispatch (ullsam_gemm_act_panels_query).  (False, False) with the switch off, outside bf16 and while autograd records
+    (the training step keeps row-major activations)."""
+    if not _ACT_PANELS or dtype != torch.bfloat16 or torch.is_grad_enabled():
+        return False, False
+    import ctypes
+    ra, wc = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.call("ullsam_gemm_act_panels_query", dt_code(dtype), M, N, K, 4 if rope else act, int(out_f32), int(bias), int(residual), 1, 128 << 20,
+              ctypes.addressof(ra), ctypes.addressof(wc))
+    return bool(ra.value), bool(wc.value)
+
+
+def empty_activation_panels(M: int, K: int, device) -> torch.Tensor:
+    """The buffer a producer writes M rows of K bf16 elements into as panels: [ceil(M / 16) * 16, K], 1 KiB aligned (packing.empty_activation_panels)."""
+    from .packing import empty_activation_panels as _e
+    return _e(M, K, device)
+
+
 def _gemm_workspace(device) -> torch.Tensor:
     """Caller-owned scratch for the GEMM's split-K forms (one 128 MiB buffer per device AND stream: launches on different
     streams may overlap; the ring kernel's split-K keeps up to 8 fp32 planes of the output there, e.g. 4 x 1081 x 4096 x 4 B = 71 MB)."""
@@ -80,17 +114,24 @@ def _gemm_workspace(device) -> torch.Tensor:
 
 def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
          act: int = ACT_NONE, out_f32: bool = False, out: Optional[torch.Tensor] = None, res_row_mod: int = 0, splitk_ok: bool = False,
-         w_panels: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out[M, N'] = act(a[M,K] @ w[N,K]^T + bias) + residual   (N' = N/2 for ACT_SWIGLU).  w_panels: `w` once more as packing.pack_ring_panels lays it
+         w_panels: Optional[torch.Tensor] = None, a_panels: bool = False, out_panels: bool = False, m: Optional[int] = None) -> torch.Tensor:
+    """out[M, N'] = act(a[M,K] @ w[N,K]^T + bias) + residual   (N' = N/2 for ACT_SWIGLU).  a_panels: `a` is an activation-panel buffer ([ceil(M / 16) * 16, K],
+    empty_activation_panels) holding m rows; out_panels: the result is one (of M rows) -- both only where activation_panels_plan said so for this launch.  w_panels: `w` once more as packing.pack_ring_panels lays it
     out (bf16) -- the ring kernels read it instead of `w` where they can, every other kernel reads `w`; same bits either way.  splitk_ok: a launch of few tiles under a long K may run as K ranges
     summed apart (ULLSAM_ACT_SPLITK_OK, include/ullsam_hip.h): not bit-equal to the one-launch kernels -- the training step's frozen linears only."""
     _chk(a, "a"); _chk(w, "w", a.dtype)
     M, K = a.shape
+    if a_panels:
+        assert m is not None and a.shape[0] == (m + 15) // 16 * 16, (a.shape, m)
+        M = m
     N = w.shape[0]
     assert w.shape[1] == K, (a.shape, w.shape)
     n_out = N // 2 if act == ACT_SWIGLU else N
     odt = torch.float32 if out_f32 else a.dtype
-    if out is None:
+    if out_panels:
+        assert out is None and not out_f32
+        out = empty_activation_panels(M, n_out, a.device)
+    elif out is None:
         out = torch.empty((M, n_out), dtype=odt, device=a.device)
     else:
         _chk(out, "out", odt)
@@ -105,6 +146,12 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
     if w_panels is not None:
         _chk(w_panels, "w_panels", torch.bfloat16)
         assert w_panels.shape == w.shape and a.dtype == torch.bfloat16, (w_panels.shape, w.shape, a.dtype)
+    if a_panels or out_panels:
+        _lib.call("ullsam_gemm_act_panels", dt_code(a.dtype), a.data_ptr(), K, w.data_ptr(), K, _p(w_panels), out.data_ptr(), n_out, int(out_f32),
+                  _p(bias), _p(residual), ldr, res_row_mod, act | (ACT_SPLITK_OK if splitk_ok else 0), M, N, K, ws.data_ptr(), ws.numel(),
+                  int(a_panels), int(out_panels), _stream())
+        return out
+    if w_panels is not None:
         _lib.call("ullsam_gemm_panels", dt_code(a.dtype), a.data_ptr(), K, w.data_ptr(), K, w_panels.data_ptr(), out.data_ptr(), n_out, int(out_f32),
                   _p(bias), _p(residual), ldr, res_row_mod, act | (ACT_SPLITK_OK if splitk_ok else 0), M, N, K, ws.data_ptr(), ws.numel(), _stream())
         return out
@@ -148,10 +195,20 @@ def gemm_fp8(a8: torch.Tensor, a_scale: torch.Tensor, w8: torch.Tensor, w_scale:
 
 def norm(x: torch.Tensor, w: Optional[torch.Tensor], b: Optional[torch.Tensor], eps: float, out_dtype: torch.dtype,
          rms: bool = False, act: int = ACT_NONE, post_scale: Optional[torch.Tensor] = None,
-         post_shift: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+         post_shift: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_panels: bool = False) -> torch.Tensor:
+    """out_panels: the bf16 result as an activation-panel buffer [ceil(rows / 16) * 16, D] for the ring GEMM that reads it (activation_panels_plan said so)."""
     _chk(x, "x")
     D = x.shape[-1]
     rows = x.numel() // D
+    if out_panels:
+        assert out is None and out_dtype == torch.bfloat16
+        out = empty_activation_panels(rows, D, x.device)
+        for t in (w, b, post_scale, post_shift):
+            if t is not None:
+                _chk(t, "norm param", torch.float32)
+        _lib.call("ullsam_norm_panels", x.data_ptr(), dt_code(x.dtype), D, out.data_ptr(), _p(w), _p(b), rows, D, float(eps), int(rms), act,
+                  _p(post_scale), _p(post_shift), 1, _stream())
+        return out
     if out is None:
         out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
     for t in (w, b, post_scale, post_shift):
@@ -496,12 +553,13 @@ def rope_split(qkv, k_cache, v_cache, pos, cos_tab, sin_tab, B, S, KVH, G, hd, c
 
 
 def gemm_qkv_rope(x: torch.Tensor, wqkv: torch.Tensor, bias: Optional[torch.Tensor], k_cache, v_cache, pos, cos_tab, sin_tab, B, S, KVH, G,
-                  cache_pos0, w_panels: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """q = rope(split(x @ wqkv^T + bias)) with k (rotated) / v appended to the caches, all in the GEMM's epilogue (head_dim 128)."""
+                  cache_pos0, w_panels: Optional[torch.Tensor] = None, a_panels: bool = False) -> torch.Tensor:
+    """q = rope(split(x @ wqkv^T + bias)) with k (rotated) / v appended to the caches, all in the GEMM's epilogue (head_dim 128).
+    a_panels: x is an activation-panel buffer of B * S rows (see gemm)."""
     _chk(x, "x"); _chk(wqkv, "wqkv", x.dtype); _chk(pos, "position_ids", torch.int32); _chk(cos_tab, "cos", torch.float32); _chk(sin_tab, "sin", torch.float32)
     _chk(k_cache, "k_cache", x.dtype); _chk(v_cache, "v_cache", x.dtype)
     K = x.shape[1]
-    assert wqkv.shape == (KVH * (G + 2) * 128, K) and x.shape[0] == B * S and cos_tab.shape[1] == 128
+    assert wqkv.shape == (KVH * (G + 2) * 128, K) and x.shape[0] == ((B * S + 15) // 16 * 16 if a_panels else B * S) and cos_tab.shape[1] == 128
     if bias is not None:
         _chk(bias, "bias", torch.float32)
     q = torch.empty((B * S, KVH * G * 128), dtype=x.dtype, device=x.device)
@@ -509,6 +567,12 @@ def gemm_qkv_rope(x: torch.Tensor, wqkv: torch.Tensor, bias: Optional[torch.Tens
     if w_panels is not None:   # wqkv once more as packing.pack_ring_panels lays it out (see gemm)
         _chk(w_panels, "w_panels", torch.bfloat16)
         assert w_panels.shape == wqkv.shape and x.dtype == torch.bfloat16
+    if a_panels:
+        _lib.call("ullsam_gemm_qkv_rope_act_panels", dt_code(x.dtype), x.data_ptr(), K, wqkv.data_ptr(), K, _p(w_panels), _p(bias), B, S, K, KVH, G, pos.data_ptr(),
+                  cos_tab.data_ptr(), sin_tab.data_ptr(), cos_tab.shape[0], q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.shape[2],
+                  cache_pos0, ws.data_ptr(), ws.numel(), 1, _stream())
+        return q
+    if w_panels is not None:
         _lib.call("ullsam_gemm_qkv_rope_panels", dt_code(x.dtype), x.data_ptr(), K, wqkv.data_ptr(), K, w_panels.data_ptr(), _p(bias), B, S, K, KVH, G, pos.data_ptr(),
                   cos_tab.data_ptr(), sin_tab.data_ptr(), cos_tab.shape[0], q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.shape[2],
                   cache_pos0, ws.data_ptr(), ws.numel(), _stream())

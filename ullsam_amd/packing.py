@@ -33,6 +33,41 @@ def unpack_ring_panels(p: torch.Tensor) -> torch.Tensor:
     return p.view(N // 16, K // 32, 16, 32).permute(0, 2, 1, 3).reshape(N, K).contiguous()
 
 
+def empty_activation_panels(M: int, K: int, device) -> torch.Tensor:
+    """An uninitialised bf16 activation-panel buffer for M rows of K elements: shape [ceil(M / 16) * 16, K], 1 KiB aligned.  The rows past M are padding: the
+    producers never write them and no consumer lets them reach a stored value, so they need no zero fill."""
+    if K % 32 != 0 or M <= 0:
+        raise ValueError(f"empty_activation_panels: M > 0 and K % 32 == 0 needed, got {M} x {K}")
+    Mp = (M + 15) // 16 * 16
+    buf = torch.empty(Mp * K + 512, dtype=torch.bfloat16, device=device)   # (the caching allocator aligns to 512 bytes only)
+    skip = (-buf.data_ptr() % 1024) // 2
+    return buf[skip:skip + Mp * K].view(Mp, K)
+
+
+def pack_activation_panels(x: torch.Tensor) -> torch.Tensor:
+    """[M, K] bf16 -> the ring GEMM's activation K-panels [ceil(M / 16)][K / 32][16 rows][32 k] (pack_ring_panels' cell, the row count rounded up to 16): row r,
+    element k sits at ((r // 16) * (K // 32) + k // 32) * 512 + (r % 16) * 32 + k % 32.  The result has the shape [ceil(M / 16) * 16, K] (padding rows zero here)
+    and starts on a 1 KiB boundary.  For tests and tools: in the product the producing kernel writes this layout, nothing repacks."""
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or x.shape[1] % 32 != 0:
+        raise ValueError(f"pack_activation_panels: bf16 [M, K] with K % 32 == 0 needed, got {x.dtype} {tuple(x.shape)}")
+    M, K = x.shape
+    out = empty_activation_panels(M, K, x.device)
+    Mp = out.shape[0]
+    src = x.detach()
+    if Mp != M:
+        src = torch.cat([src, torch.zeros((Mp - M, K), dtype=x.dtype, device=x.device)])
+    out.view(Mp // 16, K // 32, 16, 32).copy_(src.reshape(Mp // 16, 16, K // 32, 32).permute(0, 2, 1, 3))
+    return out
+
+
+def unpack_activation_panels(p: torch.Tensor, M: int) -> torch.Tensor:
+    """The row-major [M, K] activation of a panel buffer [ceil(M / 16) * 16, K]."""
+    Mp, K = p.shape
+    if p.dtype != torch.bfloat16 or K % 32 != 0 or Mp != (M + 15) // 16 * 16:
+        raise ValueError(f"unpack_activation_panels: a bf16 panel buffer of {M} rows needed, got {p.dtype} {tuple(p.shape)}")
+    return p.view(Mp // 16, K // 32, 16, 32).permute(0, 2, 1, 3).reshape(Mp, K)[:M].contiguous()
+
+
 def pack_conv3x3(w: torch.Tensor) -> torch.Tensor:
     """Conv2d weight [Cout, Cin, 3, 3] -> [Cout, (ky, kx, Cin)] matching ullsam_im2col3x3's column order."""
     return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
