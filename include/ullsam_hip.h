@@ -240,11 +240,15 @@ int ullsam_norm_fanout(const float* in, long rows, int D, const float* w, const 
                        void* out_c_pe, int c_dtype, const float* pe, long pe_rows, void* stream);
 
 /* SAM ViT attention on packed qkv [B, gh*gw, 3*heads*hd]; window > 0 fuses window_partition/unpartition and the pad-token
- * semantics; decomposed rel-pos computed in-kernel.  image_encoder.py:170-177,224-240,243-289,292-361. */
+ * semantics; decomposed rel-pos computed in-kernel.  image_encoder.py:170-177,224-240,243-289,292-361.
+ * Rel-pos tables, in the activation dtype, one size per side: global (window == 0) rel_h is [2*grid_h - 1, hd] and rel_w is
+ * [2*grid_w - 1, hd] (index q - k + side - 1; grid_h != grid_w is allowed, both <= 64); windows (window <= 14) take [2*window - 1, hd]
+ * for both, whatever the grid.  qkv, out, rel_h, rel_w and qkv_bias must be 16-byte aligned; another base is refused before any launch. */
 int ullsam_vit_attention(int dtype, const void* qkv, void* out, const void* rel_h, const void* rel_w, const void* qkv_bias,
                          int B, int heads, int hd, int grid_h, int grid_w, int window, void* stream);
 
-/* InternLM2 causal GQA attention (prefill), additive masks as modeling_internlm2.py:96-125,830-851; :383-419. */
+/* InternLM2 causal GQA attention (prefill), additive masks as modeling_internlm2.py:96-125,830-851; :383-419.
+ * q, k, v and out must be 16-byte aligned; another base is refused before any launch. */
 int ullsam_causal_attention(int dtype, const void* q, const void* k, const void* v, void* out, const int* key_mask, int B,
                             int H, int KVH, int hd, int Sq, int Sk, int k_cap, int q_pos0, void* stream);
 

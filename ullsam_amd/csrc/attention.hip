@@ -318,11 +318,14 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES == 8 ? 1 : 2) void flash_attn_k
         }
         __syncthreads();
     } else     if (REL) {
-        const int NE = 2 * G - 1;  // rows per table (<= 127)
 #pragma unroll 1
         for (int it = 0; it < 2; ++it) {
             const int tb = FAST64 ? 1 - it : it;  // FAST64: width table first (its slab is then recycled for rel_h)
             const T* const tab = reinterpret_cast<const T*>(tb == 0 ? p.rel_h : p.rel_w);   // (a select, not an indexed pointer array: that array lived in scratch)
+            // each table has its own size: rel_h is [2*grid_h - 1, HD] with index q - k + (grid_h - 1), rel_w is [2*grid_w - 1, HD] with
+            // q - k + (grid_w - 1) (get_rel_pos per side, image_encoder.py:292-322); the same on a square grid
+            const int GK = tb == 0 ? GHk : G;
+            const int NE = 2 * GK - 1;  // rows of this table (<= 127)
             __syncthreads();
             // stage table rows 0..127 into the contiguous K|V region (128 rows of RS bytes)
             for (int idx = tid; idx < 128 * CPR; idx += NT) {
@@ -333,7 +336,6 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES == 8 ? 1 : 2) void flash_attn_k
             }
             __syncthreads();
             const int qc = tb == 0 ? qh : qw;
-            const int GK = tb == 0 ? GHk : G;
             float* dst = tb == 0 ? relh : relw;
             const int ntile = (NE + 31) / 32;
 #pragma unroll 1
@@ -349,7 +351,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES == 8 ? 1 : 2) void flash_attn_k
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int e = 32 * t + crow32(r, h);
-                    const int kk = qc + (G - 1) - e;  // rel index e = q - k + (G-1)  (get_rel_pos, image_encoder.py:318-322)
+                    const int kk = qc + (GK - 1) - e;  // rel index e = q - k + (GK-1)  (get_rel_pos, image_encoder.py:318-322)
                     if (e < NE && kk >= 0 && kk < GK) dst[kk * 32 + ql] = acc[r] * LOG2E;  // tables are kept in log2 units
                 }
             }
@@ -1894,6 +1896,10 @@ extern "C" int ullsam_vit_attention(int dtype, const void* qkv, void* out, const
     ULLSAM_CHECK(grid_h <= 64 && grid_w <= 64 && window <= 14, "vit_attention: grid %dx%d / window %d too large", grid_h, grid_w, window);
     const int esz = dtype == 0 ? 4 : 2;
     ULLSAM_CHECK((hd * esz) % 16 == 0, "vit_attention: head_dim*elem must be a multiple of 16 bytes");
+    // every kernel behind this entry point, the tiled ones included, reads qkv, the rel-pos tables and the pad tokens' bias 16 bytes at a time and
+    // stores 8 or 16: an unaligned base is refused here, before any launch
+    ULLSAM_CHECK((((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)qkv_bias | (uintptr_t)rel_h | (uintptr_t)rel_w) & 15) == 0,
+                 "vit_attention: qkv, out, rel_h, rel_w and qkv_bias must be 16-byte aligned");
     const long D = (long)heads * hd;
     const long N = (long)grid_h * grid_w;
     AttnArgs a = {};
@@ -1915,7 +1921,7 @@ extern "C" int ullsam_vit_attention(int dtype, const void* qkv, void* out, const
         // SAM's own shape (14x14 windows, head_dim 80, bf16): the whole-window kernel; variant 2 forces the tiled kernel for A/B
         a.q_pos0 = (g_attn_variant >= 3 && g_attn_variant <= 8) ? g_attn_variant - 3 : 2;  // stagger of the second resident workgroup, units of s_sleep(127) = 3.4 us (A/B: variant 3 + n)
         // round 5: window rows as 16-wide query groups / key tiles, no key-block chain (win14r_attn_kernel); variant 13 keeps round 1's 32-query kernel (A/B, equality test)
-        if (dtype == 1 && window == 14 && hd == 80 && g_attn_variant != 1 && g_attn_variant != 2 && g_attn_variant != 13 && (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)qkv_bias | (uintptr_t)rel_h | (uintptr_t)rel_w) & 15) == 0) {   // (the kernel reads the rel-pos tables 16 bytes at a time too)
+        if (dtype == 1 && window == 14 && hd == 80 && g_attn_variant != 1 && g_attn_variant != 2 && g_attn_variant != 13) {
             a.q_pos0 = (g_attn_variant >= 3 && g_attn_variant <= 8) ? g_attn_variant - 3 : 0;
             a.dbg = g_attn_dbg;
             return launch_win14r(a, s);
@@ -1930,7 +1936,7 @@ extern "C" int ullsam_vit_attention(int dtype, const void* qkv, void* out, const
     // staging traffic, LDS writes and barriers per score) -- identical results, 543 vs 576 us per ViT-H layer at batch 4 (same-process A/B,
     // tools/probes/attn8_check.py); variant 9 keeps the two 4-wave workgroups with 64-key tiles
     // SAM ViT-H's own shape (head_dim 80): the LDS-DMA kernel; variant 12 keeps the tiled 8-wave kernel (bit-equality test, A/B)
-    if (dtype == 1 && grid_h == 64 && grid_w == 64 && hd == 80 && g_attn_variant != 9 && g_attn_variant != 12 && (((uintptr_t)qkv | (uintptr_t)out) & 15) == 0)
+    if (dtype == 1 && grid_h == 64 && grid_w == 64 && hd == 80 && g_attn_variant != 9 && g_attn_variant != 12)
         return launch_vitglob(a, s);
     if (dtype == 1 && grid_h == 64 && grid_w == 64 && g_attn_variant != 9) return dispatch_hd<bf16, MODE_VIT_GLOBAL, 8>(a, hd, s);
     return dtype == 0 ? dispatch_hd<float, MODE_VIT_GLOBAL, 4>(a, hd, s) : dispatch_hd<bf16, MODE_VIT_GLOBAL, 4>(a, hd, s);
@@ -1942,6 +1948,9 @@ extern "C" int ullsam_causal_attention(int dtype, const void* q, const void* k, 
                                        int B, int H, int KVH, int hd, int Sq, int Sk, int k_cap, int q_pos0, void* stream) {
     ULLSAM_CHECK(dtype == 0 || dtype == 1, "causal_attention: bad dtype");
     ULLSAM_CHECK(H % KVH == 0, "causal_attention: H %% KVH != 0");
+    // every kernel behind this entry point, the tiled ones included, reads q / k / v 16 bytes at a time and stores 8 or 16: an unaligned base is
+    // refused here, before any launch
+    ULLSAM_CHECK((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0, "causal_attention: q, k, v and out must be 16-byte aligned");
     AttnArgs a = {};
     a.q = q; a.k = k; a.v = v; a.out = out;
     a.q_bs = (long)Sq * H * hd; a.q_ts = (long)H * hd; a.q_hs = hd;
@@ -1953,7 +1962,7 @@ extern "C" int ullsam_causal_attention(int dtype, const void* q, const void* k, 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // bf16, head_dim 128, contiguous 256-byte key rows (the KV-cache layout): the LDS-DMA kernel (variant 11 keeps the tiled kernel, for the
     // bit-equality test and A/B)
-    if (dtype == 1 && hd == 128 && g_attn_variant != 11 && a.k_ts == 128 && a.v_ts == 128 && (((uintptr_t)k | (uintptr_t)v | (uintptr_t)q | (uintptr_t)out) & 15) == 0)
+    if (dtype == 1 && hd == 128 && g_attn_variant != 11 && a.k_ts == 128 && a.v_ts == 128)
         return launch_causal128(a, s);
     return dtype == 0 ? dispatch_hd<float, MODE_CAUSAL, 4>(a, hd, s) : dispatch_hd<bf16, MODE_CAUSAL, 4>(a, hd, s);
 }
