@@ -568,6 +568,25 @@ int ullsam_split_round(const unsigned long long* keys, const int* vals, long cap
 int ullsam_split_collect(const int* labels, const int* up, long n, long K, unsigned long long* list, long room, int* flags, void* stream);
 int ullsam_split_relabel(const unsigned long long* list, long parts, const int* labels, const int* d2, const int* up, int H, int W, long K,
                          int* newid, int* out, int* parent, int* peak_r2, int* peak_xy, int* parts_of, int* flags, void* stream);
+/* The same split of a label volume (csrc/split3d.hip; integer work, bit-exact with the host form utils.split3d.split_labels3d; definition in
+   DESIGN.md "7b, continued (3-D splitting)").  labels i32 [Z, H, W] with ids 0..K, 0 = background, 1 <= Z, H, W <= 32767 and
+   n = Z * H * W <= 32767^2 (the bound of split_flatten / split_round / split_collect, which run on the flattened volume as they are);
+   d2 i32 [Z, H, W] = distance3d_x's mode 0 of the same volume; p = (z * H + y) * W + x; key(p) = (d2[p], -p).  flags i32 [8] with split_*'s
+   meanings.
+   split3d_ascent: up i32 [Z, H, W][p] = the voxel of greatest key among p and its 26 neighbours with p's label; p on the background and on
+     a label outside 1..K (flags[0]).  route 0 / 1: a workgroup stages its 64 x 4 x 4 voxels and a one-voxel halo in LDS (the volume's outside
+     enters as label 0); 2: global memory.  The output does not depend on the route.
+   split3d_passes: split_passes' table (same layout, same flags; cap a power of two >= 2 * max_pairs; keys and vals are zeroed here) over the
+     13 forward neighbours (dz, dy, dx) > (0, 0, 0): every 26-adjacent voxel pair of one label whose roots a < b differ (up flattened) sends
+     min(d2, d2) to the maximum under key a << 32 | b.  The table goes into split_round as it is.
+   split3d_relabel: list u64 [parts] (split_collect's, sorted ascending).  Part i gets id i + 1: parent i32 [parts], peak_r2 i32 [parts] = d2 at
+     its representative p, peak_xyz i32 [parts, 3] = (p % W, (p / W) % H, p / (W * H)), parts_of i32 [K] (zeroed here); newid i32 [Z, H, W] is
+     scratch; out i32 [Z, H, W][p] = the id of up[p]'s part, 0 on the background. */
+int ullsam_split3d_ascent(const int* labels, const int* d2, int Z, int H, int W, long K, int route, int* up, int* flags, void* stream);
+int ullsam_split3d_passes(const int* labels, const int* d2, const int* up, int Z, int H, int W, long K, unsigned long long* keys, int* vals, long cap,
+                          int max_pairs, int* flags, void* stream);
+int ullsam_split3d_relabel(const unsigned long long* list, long parts, const int* labels, const int* d2, const int* up, int Z, int H, int W, long K,
+                           int* newid, int* out, int* parent, int* peak_r2, int* peak_xyz, int* parts_of, int* flags, void* stream);
 /* Outlines of a label image: every instance as closed polygon loops on the pixel lattice (csrc/outline.hip; integer work, bit-exact with the
    host form utils.outline.label_outlines; definition in DESIGN.md "7b, continued (outlines)").  labels i32 [H, W] with ids 0..K, 0 =
    background, 1 <= H, W and n = H * W < 2^29; p = y * W + x.  Side s of a pixel of label k > 0 whose 4-neighbour is not k (the frame's outside

@@ -128,6 +128,9 @@ SIGNATURES = {
     "ullsam_split_round": [vp, vp, i64, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp],
     "ullsam_split_collect": [vp, vp, i64, i64, vp, i64, vp, vp],
     "ullsam_split_relabel": [vp, i64, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp],
+    "ullsam_split3d_ascent": [vp, vp, i32, i32, i32, i64, i32, vp, vp, vp],
+    "ullsam_split3d_passes": [vp, vp, vp, i32, i32, i32, i64, vp, vp, i64, i32, vp, vp],
+    "ullsam_split3d_relabel": [vp, i64, vp, vp, vp, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp],
     "ullsam_outline_sides": [vp, i32, i32, i64, vp, vp, vp, vp, vp],
     "ullsam_outline_scan": [vp, i64, vp, vp, vp, vp],
     "ullsam_outline_successors": [vp, i32, i32, vp, vp, i64, i32, vp, vp, vp, vp, vp],

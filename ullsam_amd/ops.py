@@ -1513,6 +1513,68 @@ def split_relabel(parts_sorted: torch.Tensor, labels: torch.Tensor, d2: torch.Te
     return out, parent, peak_r2, peak_xy, parts_of, flags
 
 
+# ---- the same split of a label volume (csrc/split3d.hip; utils.split3d drives these, with split_flatten / split_round / split_collect) ----------
+SPLIT3D_MAX_VOXELS = 32767 * 32767    # the bound of the flat split entry points; every neighbour index stays inside int32
+
+
+def _split3d_volume(volume: torch.Tensor, num, what: str):
+    z, h, w, k = _distance3d_volume(volume, num, what)
+    if z * h * w > SPLIT3D_MAX_VOXELS:
+        raise _lib.UllsamError(f"{what}: a volume of {z} x {h} x {w} = {z * h * w} voxels (at most 32767^2 = {SPLIT3D_MAX_VOXELS})")
+    return z, h, w, k
+
+
+def split3d_ascent(volume: torch.Tensor, d2: torch.Tensor, num: Optional[int] = None, route: str = "auto", flags: Optional[torch.Tensor] = None):
+    """volume, d2 int32 [Z, H, W] (d2 = distance3d_x's "inner" map) -> (up int32 [Z, H, W], flags int32 [8]): up[p] = the linear index of the voxel
+    of greatest (d2, -index) among p and its 26 neighbours with p's label; p itself on the background (ullsam_hip.h split3d_ascent).  route "auto"
+    / "lds" / "global": where the 3 x 3 x 3 neighbourhood is read from; the output does not depend on it."""
+    z, h, w, k = _split3d_volume(volume, num, "split3d_ascent")
+    _split_map(d2, "d2", volume)
+    flags = _split_flags(flags, volume.device)
+    up = torch.empty((z, h, w), dtype=torch.int32, device=volume.device)
+    _lib.call("ullsam_split3d_ascent", volume.data_ptr(), d2.data_ptr(), z, h, w, k, SPLIT_ROUTES[route], up.data_ptr(), flags.data_ptr(), _stream())
+    return up, flags
+
+
+def split3d_passes(volume: torch.Tensor, d2: torch.Tensor, up: torch.Tensor, max_pairs: int, num: Optional[int] = None, flags: Optional[torch.Tensor] = None):
+    """up flattened -> (keys int64 [slots] -- smaller root << 32 | larger root, 0 = empty --, vals int32 [slots] = the pass: the largest min(d2, d2)
+    over the 26-adjacent voxel pairs of one label across the two basins, flags): split_passes' table; the caller reads flags[1], flags[2]."""
+    z, h, w, k = _split3d_volume(volume, num, "split3d_passes")
+    _split_map(d2, "d2", volume); _split_map(up, "up", volume)
+    max_pairs = int(max_pairs)
+    if not 1 <= max_pairs <= 2 ** 30:
+        raise _lib.UllsamError(f"split3d_passes: max_pairs must lie in 1..2^30, got {max_pairs}")
+    dev = volume.device
+    cap = mosaic_table_slots(max_pairs)
+    keys = torch.empty((cap,), dtype=torch.int64, device=dev)
+    vals = torch.empty((cap,), dtype=torch.int32, device=dev)
+    flags = _split_flags(flags, dev)
+    _lib.call("ullsam_split3d_passes", volume.data_ptr(), d2.data_ptr(), up.data_ptr(), z, h, w, k, keys.data_ptr(), vals.data_ptr(), cap, max_pairs,
+              flags.data_ptr(), _stream())
+    return keys, vals, flags
+
+
+def split3d_relabel(parts_sorted: torch.Tensor, volume: torch.Tensor, d2: torch.Tensor, up: torch.Tensor, num: int, flags: Optional[torch.Tensor] = None):
+    """parts_sorted int64 [K'] (split_collect's list, sorted), up flattened -> (out int32 [Z, H, W], parent int32 [K'], peak_r2 int32 [K'], peak_xyz
+    int32 [K', 3], parts_of int32 [num], flags): part i gets id i + 1 (ullsam_hip.h split3d_relabel)."""
+    z, h, w, k = _split3d_volume(volume, num, "split3d_relabel")
+    _chk(parts_sorted, "parts_sorted", torch.int64); _split_map(d2, "d2", volume); _split_map(up, "up", volume)
+    if k > MOSAIC_MAX_IDS:
+        raise _lib.UllsamError("split3d_relabel: num must lie in 0..2^31 - 2")
+    dev = volume.device
+    n = parts_sorted.numel()
+    out = torch.empty((z, h, w), dtype=torch.int32, device=dev)
+    newid = torch.empty((z, h, w), dtype=torch.int32, device=dev)
+    parent = torch.empty((n,), dtype=torch.int32, device=dev)
+    peak_r2 = torch.empty((n,), dtype=torch.int32, device=dev)
+    peak_xyz = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    parts_of = torch.empty((k,), dtype=torch.int32, device=dev)
+    flags = _split_flags(flags, dev)
+    _lib.call("ullsam_split3d_relabel", _p(parts_sorted) if n else None, n, volume.data_ptr(), d2.data_ptr(), up.data_ptr(), z, h, w, k, newid.data_ptr(),
+              out.data_ptr(), parent.data_ptr(), peak_r2.data_ptr(), peak_xyz.data_ptr(), _p(parts_of) if k else None, flags.data_ptr(), _stream())
+    return out, parent, peak_r2, peak_xyz, parts_of, flags
+
+
 # ---- outlines of a label image: polygon loops (csrc/outline.hip; utils.outline drives these) --------------------------------------------------
 OUTLINE_FLAGS = 8          # bad id / index, E, corners, leaders, list cursor, parent chain too long, (two free)
 OUTLINE_MAX_PIXELS = 2 ** 29
