@@ -710,6 +710,29 @@ int ullsam_measure_instances(const int* labels, int H, int W, int K, const void*
                              void* stream);
 int ullsam_label_contacts(const int* labels, int H, int W, int K, unsigned long long* keys, long* counts, long cap, int max_pairs, long* rows,
                           int* flags, void* stream);
+/* Per-object measurements and contacts from a label VOLUME (csrc/measure3d.hip; integer work, bit-exact with the host forms
+   utils.measure3d.measure_objects / object_contacts; definition in DESIGN.md "7b, continued (3-D measurements)").  volume i32 [Z, H, W] with
+   ids 0..K, 0 = background, 1 <= Z, H, W <= 32767 and Z * H * W <= 2^31 - 1 (x * x < 2^30 and every count < 2^31: every coordinate sum stays
+   below 2^61, sum v^2 below 65535^2 (2^31 - 1) < 2^63), K <= 2^31 - 2.  Row k - 1 of every table belongs to id k; both entries set all of
+   their outputs themselves (init kernels), the caller zeroes nothing.
+   flags i32 [4]: [0] = 1 when an id lies outside 0..K (it reads as background; no table is indexed with it), [1] = 1 when the pair table
+   refused a key, [2] = the number of distinct pairs, [3] = the number of rows object_contacts3d wrote.
+   measure_objects3d: voxels i64 [K]; box i32 [K, 6] inclusive (x0, y0, z0, x1, y1, z1), (INT_MAX, INT_MAX, INT_MAX, -1, -1, -1) for an absent
+     id; moments i64 [K, 9] = sum x, y, z, x^2, y^2, z^2, xy, xz, yz in voxel indices; surface i64 [K, 7] = boundary voxels (voxels of k with
+     a 6-neighbour that is not k), fz, fy, fx (voxel faces of k normal to that axis facing "not k"), cz, cy, cx (those facing another object);
+     the volume's outside is "not k" and is no object.  intensity: NULL with channels = 0, else u8 (sample_bytes 1) or u16 (2) interleaved
+     [Z, H, W, channels], channels <= 4, any element-aligned address: isum / isum2 i64 [K, channels] = sum v, sum v^2; imin / imax i32
+     [K, channels], (INT_MAX, -1) for an absent id.  lds_slots: the entries of the per-workgroup LDS table the runs are summed in before one
+     global atomic per quantity and id (0 or a power of two <= 128; 0 = every run straight to the global tables; the results are the same).
+   object_contacts3d: keys u64 [cap] / counts i64 [cap, 3]: the open-addressing pair table (key a << 32 | b, 0 < a < b; cap a power of two
+     >= 2 * max_pairs), counts = (nz, ny, nx), the faces normal to each axis shared by a voxel of a and its neighbour voxel of b, every
+     adjacent voxel pair counted once (looking forward along each axis); rows i64 [max_pairs, 4] = (key, nz, ny, nx) of the claimed slots in
+     no particular order, flags[3] of them. */
+int ullsam_measure_objects3d(const int* volume, int Z, int H, int W, int K, const void* intensity, int channels, int sample_bytes, int lds_slots,
+                             long* voxels, int* box, long* moments, long* surface, long* isum, long* isum2, int* imin, int* imax, int* flags,
+                             void* stream);
+int ullsam_object_contacts3d(const int* volume, int Z, int H, int W, int K, unsigned long long* keys, long* counts, long cap, int max_pairs,
+                             long* rows, int* flags, void* stream);
 
 /* Point prompts, boxes and per-instance masks from one instance label image (csrc/prompts.hip; the reference's dataset loop
    train_joint_v2.py:313-468 as integer kernels, bit-exact with utils.prompts' host route; definitions in DESIGN.md "7b, continued (prompts)").

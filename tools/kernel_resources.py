@@ -59,8 +59,10 @@ HOT_RASTER = [r"raster_edges_kernel", r"raster_sums_kernel", r"raster_scan_sums_
 HOT_DISTANCE3D = [r"dist3_z_kernelILb[01]E", r"dist3_y_kernelILb[01]E", r"dist3_x_kernelILi\dE", r"dist3_depth_decode_kernel"]
 # splitting the touching objects of a label volume (csrc/split3d.hip): both routes of the 26-neighbour ascent, the 13-neighbour passes, tables, relabel
 HOT_SPLIT3D = [r"split3_ascent_kernelILb[01]E", r"split3_passes_kernel", r"split3_tables_kernel", r"split3_relabel_kernel"]
+# per-object measurements and contacts from a label volume (csrc/measure3d.hip): the tile kernel for 0..4 channels, the contacts, init and compaction
+HOT_MEASURE3D = [r"measure3d_kernelILi\dE", r"contacts3d_kernel", r"measure3d_init_kernel", r"contacts3d_init_kernel", r"contacts3d_compact_kernel"]
 HOT_BF16 = (HOT_BF16 + HOT_AMG + HOT_REGIONS + HOT_DECODE_FP8 + HOT_LABELS + HOT_MEASURE + HOT_DISTANCE + HOT_SPLIT + HOT_OUTLINE + HOT_RASTER
-            + HOT_DISTANCE3D + HOT_SPLIT3D)
+            + HOT_DISTANCE3D + HOT_SPLIT3D + HOT_MEASURE3D)
 HOT = HOT_BF16
 # round 6: the persistent ring kernel (<MI0, MI1, NTW, EMODE, STAMP = false>: the six shapes without stamps): no spilled VECTOR register and no scratch.  Its tile loop keeps more scalars than the 102 SGPRs hold
 # (tile coordinates, two buffer descriptors, the kernel arguments the epilogue reads): hipcc parks the overflow in lanes of a VGPR (v_writelane / v_readlane, outside the K loop) -- counted as

@@ -154,6 +154,8 @@ SIGNATURES = {
     "ullsam_raster_finish": [vp, i32, i32, vp, i64, vp, vp, vp, vp, vp],
     "ullsam_measure_instances": [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "ullsam_label_contacts": [vp, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp],
+    "ullsam_measure_objects3d": [vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "ullsam_object_contacts3d": [vp, i32, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp],
     "ullsam_label_d1": [vp, i32, i32, i32, vp, vp, vp, vp],
     "ullsam_prompt_choose": [vp, i32, C.c_ulonglong, vp, vp, vp, vp, vp],
     "ullsam_prompt_sets": [vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],

@@ -507,7 +507,7 @@ class SamAutomaticMaskGenerator:
 
     @torch.no_grad()
     def generate_stack_label_volume(self, images, order: str = "area", min_visible_area: int = 0, iou=(1, 4), mode: str = "mutual",
-                                    min_planes: int = 1, min_volume: int = 0):
+                                    min_planes: int = 1, min_volume: int = 0, measure: bool = False):
         """Segment everything on every plane of a z-stack or every frame of a time-lapse, then link the per-plane instances along the third axis
         into 3-D objects: every plane goes through generate_label_map(plane, order=order, min_visible_area=min_visible_area), its label map stays
         on the device, and utils.stack.link_label_stack (csrc/stack.hip) links two labels of consecutive planes when their IoU is at least
@@ -518,6 +518,8 @@ class SamAutomaticMaskGenerator:
         map.  objects = {"voxels" int64 [K], "zrange" int32 [K, 2], "boxes" int32 [K, 4], "label_of_global" int32 [G + 1]} as link_label_stack
         returns them (utils.stack.track_table(label_of_global, counts) turns the last into the [K, Z] index of per-plane labels).
         A stack of one plane returns that plane's generate_label_map labels exactly.
+        measure=True: a fourth value, the utils.measure3d.ObjectTable of `volume` against the stack, every plane of which must then be H x W x 3
+        uint8 (it is measured as the caller passed it); the tables stay on the device.
         Not done here: an object missing from a plane is not bridged (it comes back as a new object), divisions are no events, planes are not
         sharded over ranks, and the whole label stack has to fit in device memory."""
         from .utils import stack as K
@@ -525,6 +527,9 @@ class SamAutomaticMaskGenerator:
             raise ValueError(f"generate_stack_label_volume: an array of images must be [Z, H, W, 3], got {tuple(images.shape)}")
         if len(images) < 1:
             raise ValueError("generate_stack_label_volume: no planes")
+        if measure:
+            for z in range(len(images)):
+                _measure_image_check(images[z], "generate_stack_label_volume")
         dev = self.model.device
         planes, records, counts = None, [], []
         for z in range(len(images)):
@@ -547,4 +552,9 @@ class SamAutomaticMaskGenerator:
             for r in recs:
                 r["object"] = int(lut[base[z] + r["label"]]) if r["label"] else 0
                 out.append(r)
-        return volume, out, {"voxels": voxels, "zrange": zrange, "boxes": boxes, "label_of_global": label_of_global}
+        objects = {"voxels": voxels, "zrange": zrange, "boxes": boxes, "label_of_global": label_of_global}
+        if measure:
+            from .utils import measure3d as M3
+            stack = torch.stack([torch.as_tensor(np.ascontiguousarray(im) if isinstance(im, np.ndarray) else im) for im in images])
+            return volume, out, objects, M3.measure_objects(volume, stack, num=len(voxels), device=dev)
+        return volume, out, objects

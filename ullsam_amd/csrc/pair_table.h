@@ -77,6 +77,28 @@ __device__ __forceinline__ void mz_pair_add(mz_u64 key, int n, mz_u64* __restric
     }
     mz_store(flags + 1, 1);
 }
+// The same table with three 64-bit counts per key, counts i64 [mask + 1, 3] (measure3d.hip: the faces two objects share, per axis): adds n at
+// 3 * slot + axis.
+__device__ __forceinline__ void mz_pair_add_axis(mz_u64 key, int axis, int n, mz_u64* __restrict__ keys, long* __restrict__ counts, mz_u64 mask,
+                                                 int max_pairs, int* __restrict__ flags) {
+    mz_u64 slot = mz_hash(key) & mask;
+    for (mz_u64 probes = 0; probes <= mask; ++probes, slot = (slot + 1) & mask) {
+        mz_u64 old = __hip_atomic_load(keys + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == 0) {
+            if (mz_load(flags + 2) > max_pairs) break;
+            old = atomicCAS(keys + slot, 0ull, key);
+            if (old == 0) {
+                mz_add(flags + 2, 1);
+                old = key;
+            }
+        }
+        if (old == key) {
+            mz_add(counts + 3 * slot + axis, n);
+            return;
+        }
+    }
+    mz_store(flags + 1, 1);
+}
 // The same table with a maximum per key instead of a sum (split.hip: the pass between two basins); vals are zeroed by the caller and v > 0.  The
 // atomic is sent only when a relaxed load says it improves.
 __device__ __forceinline__ void mz_pair_max(mz_u64 key, int v, mz_u64* __restrict__ keys, int* __restrict__ vals, mz_u64 mask, int max_pairs,

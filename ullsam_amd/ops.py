@@ -2084,6 +2084,81 @@ def label_contacts(labels: torch.Tensor, num: int, max_pairs: int = 1 << 20, fla
     return rows, flags
 
 
+# ---- per-object measurements and contacts from a label volume (csrc/measure3d.hip; utils.measure3d drives these) ------------------------------
+MEASURE3D_MAX_SIDE = 32767            # x * x < 2^30
+MEASURE3D_MAX_VOXELS = 2 ** 31 - 1    # every count < 2^31: coordinate sums below 2^61, sum v^2 below 65535^2 (2^31 - 1) < 2^63
+MEASURE3D_TILE_R = 8                  # M3_TILE_R and M3_TILE_P of csrc/measure3d.hip: a workgroup's tile is 256 columns x 8 rows x 4 planes
+MEASURE3D_TILE_P = 4
+MEASURE3D_LDS_SLOTS = 128             # the default route: the LDS table, 2 - 3 x faster per call than 0 (tools/measure3d_bench.py, profiles/r25_measure3d.txt)
+
+
+def _measure3d_volume(volume: torch.Tensor, num: int, what: str):
+    _chk(volume, "volume", torch.int32)
+    if volume.dim() != 3:
+        raise ValueError(f"{what}: volume must be [Z, H, W], got {tuple(volume.shape)}")
+    z, h, w = volume.shape
+    if not all(1 <= n <= MEASURE3D_MAX_SIDE for n in (z, h, w)) or z * h * w > MEASURE3D_MAX_VOXELS:
+        raise _lib.UllsamError(f"{what}: a volume of {z} x {h} x {w} (each side in 1..{MEASURE3D_MAX_SIDE}, at most 2^31 - 1 voxels)")
+    if not 0 <= int(num) <= MOSAIC_MAX_IDS:
+        raise _lib.UllsamError(f"{what}: num = {num} must lie in 0..2^31 - 2")
+    return z, h, w
+
+
+def measure_objects3d(volume: torch.Tensor, num: int, intensity: Optional[torch.Tensor] = None, lds_slots: int = MEASURE3D_LDS_SLOTS,
+                      out: Optional[dict] = None, flags: Optional[torch.Tensor] = None):
+    """volume int32 [Z, H, W] with ids 0..num, intensity None or uint8 / uint16 [Z, H, W] / [Z, H, W, C <= 4] -> (dict of the tables of ullsam_hip.h:
+    voxels int64 [num], box int32 [num, 6], moments int64 [num, 9], surface int64 [num, 7] and, with an image, isum / isum2 int64 [num, C], imin /
+    imax int32 [num, C]; flags int32 [4]: the caller reads flags[0]).  lds_slots: a power of two <= 128 (the runs of equal labels are summed in a
+    per-workgroup LDS table first: the faster route as measured, tools/measure3d_bench.py) or 0 (every run straight to the global tables); same
+    results.  out: preallocated tables by name."""
+    z, h, w = _measure3d_volume(volume, num, "measure_objects3d")
+    k, dev = int(num), volume.device
+    c, nbytes = 0, 0
+    if intensity is not None:
+        if intensity.dtype not in (torch.uint8, torch.uint16):
+            raise _lib.UllsamError(f"measure_objects3d: the intensity image must be uint8 or uint16, got {intensity.dtype} (float sums depend on the order of arrival)")
+        _chk(intensity, "intensity")
+        if intensity.dim() not in (3, 4) or tuple(intensity.shape[:3]) != (z, h, w):
+            raise ValueError(f"measure_objects3d: intensity {tuple(intensity.shape)} for a volume {(z, h, w)}")
+        c = 1 if intensity.dim() == 3 else int(intensity.shape[3])
+        if not 1 <= c <= MEASURE_MAX_CHANNELS:
+            raise _lib.UllsamError(f"measure_objects3d: {c} channels (1..{MEASURE_MAX_CHANNELS})")
+        nbytes = intensity.element_size()
+    lds_slots = int(lds_slots)
+    if lds_slots < 0 or lds_slots > MEASURE_LDS_SLOTS or lds_slots & (lds_slots - 1):
+        raise _lib.UllsamError(f"measure_objects3d: lds_slots = {lds_slots} must be 0 or a power of two <= {MEASURE_LDS_SLOTS}")
+    i32, i64 = torch.int32, torch.int64
+    t = {"voxels": _out_view(out, "voxels", (k,), i64, dev), "box": _out_view(out, "box", (k, 6), i32, dev),
+         "moments": _out_view(out, "moments", (k, 9), i64, dev), "surface": _out_view(out, "surface", (k, 7), i64, dev)}
+    if c:
+        t.update(isum=_out_view(out, "isum", (k, c), i64, dev), isum2=_out_view(out, "isum2", (k, c), i64, dev),
+                 imin=_out_view(out, "imin", (k, c), i32, dev), imax=_out_view(out, "imax", (k, c), i32, dev))
+    flags = _out_i32(flags, (MEASURE_FLAGS,), dev, "flags")
+    _lib.call("ullsam_measure_objects3d", volume.data_ptr(), z, h, w, k, _p(intensity), c, nbytes, lds_slots, t["voxels"].data_ptr(), t["box"].data_ptr(),
+              t["moments"].data_ptr(), t["surface"].data_ptr(), _p(t.get("isum")), _p(t.get("isum2")), _p(t.get("imin")), _p(t.get("imax")),
+              flags.data_ptr(), _stream())
+    return t, flags
+
+
+def object_contacts3d(volume: torch.Tensor, num: int, max_pairs: int = 1 << 20, flags: Optional[torch.Tensor] = None):
+    """volume int32 [Z, H, W] with ids 0..num -> (rows int64 [max_pairs, 4] = (a << 32 | b, nz, ny, nx) of the pairs 0 < a < b and the voxel faces they
+    share per axis, in no particular order; flags int32 [4]: bad id, overflow, distinct pairs, rows written -- the caller reads them and keeps the
+    first flags[2] rows)."""
+    z, h, w = _measure3d_volume(volume, num, "object_contacts3d")
+    max_pairs = int(max_pairs)
+    if not 1 <= max_pairs <= 2 ** 30:
+        raise _lib.UllsamError(f"object_contacts3d: max_pairs must lie in 1..2^30, got {max_pairs}")
+    dev = volume.device
+    cap = mosaic_table_slots(max_pairs)
+    keys = torch.empty((cap,), dtype=torch.int64, device=dev)
+    counts = torch.empty((cap, 3), dtype=torch.int64, device=dev)
+    rows = torch.empty((max_pairs, 4), dtype=torch.int64, device=dev)
+    flags = _out_i32(flags, (MEASURE_FLAGS,), dev, "flags")
+    _lib.call("ullsam_object_contacts3d", volume.data_ptr(), z, h, w, int(num), keys.data_ptr(), counts.data_ptr(), cap, max_pairs, rows.data_ptr(),
+              flags.data_ptr(), _stream())
+    return rows, flags
+
+
 # ---- the interactive loop's display tail (csrc/interactive.hip) ---------------------------------------------------------------------
 CLICK_MAX_P = 512
 
