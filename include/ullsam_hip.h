@@ -378,8 +378,10 @@ int ullsam_resize_bilinear(const float* in, long in_plane_stride, int in_ld, int
 int ullsam_mask_iou_counts(const unsigned char* a, const unsigned char* b, unsigned long long* counts, int N, long per,
                            void* stream);                                                /* train_joint_v2.py:683-694 */
 
-/* Automatic-mask-generation helpers, bit-exact with utils/amg.py (integer / byte work) */
-int ullsam_stability_score(const float* masks, long N, long per, float mask_threshold, float threshold_offset,
+/* Automatic-mask-generation helpers, bit-exact with utils/amg.py (integer / byte work).  mask_threshold / threshold_offset are doubles: the entries
+   compare against (float)(thr + off), (float)(thr - off) and (float)thr, each rounded once from the double sum as the reference's Python floats are.  (They were floats before; ULLSAM_ABI_VERSION stayed 14 through
+   that change -- the in-tree library and binding are rebuilt together by the build stamp, a caller compiled against the old header must be recompiled.) */
+int ullsam_stability_score(const float* masks, long N, long per, double mask_threshold, double threshold_offset,
                            unsigned int* counts, float* score, void* stream);                 /* amg.py:156-176 */
 int ullsam_mask_to_box(const unsigned char* masks, long N, int H, int W, int* boxes, void* stream);   /* amg.py:303-346 */
 int ullsam_rle_pack(const unsigned char* masks, long N, int H, int W, unsigned long long* words, int* counts,
@@ -388,7 +390,7 @@ int ullsam_rle_emit(const unsigned long long* words, const int* select, long N, 
                     void* stream);                                                            /* amg.py:119-133 (nonzero -> run edges) */
 /* generator fast path: postprocess_masks + stability counts + mask->box + RLE change words in one pass, logits never stored */
 int ullsam_amg_postprocess(const float* low, const int* index, long M, int LH, int LW, int S1, int nh, int nw, int CH, int CW,
-                           int FH, int FW, int cx0, int cy0, float mask_threshold, float threshold_offset,
+                           int FH, int FW, int cx0, int cy0, double mask_threshold, double threshold_offset,
                            unsigned long long* words, int* rle_counts, unsigned char* first, int* boxes, unsigned int* stab,
                            void* stream);                      /* sam.py:154-162 + amg.py:156-176, 303-346, 107-135, 251-264 */
 int ullsam_nms_mask(const float* boxes, int N, float iou_threshold, unsigned long long* mask, void* stream); /* torchvision.ops.nms (absent dependency) */

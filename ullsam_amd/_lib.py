@@ -14,7 +14,7 @@ ABI_VERSION = 14  # == ULLSAM_ABI_VERSION in include/ullsam_hip.h (tests/test_ho
 
 _lib = None
 
-vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_long, C.c_float
+vp, i32, i64, f32, f64 = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 
 # name -> argtypes, exactly mirroring include/ullsam_hip.h
 SIGNATURES = {
@@ -88,11 +88,11 @@ SIGNATURES = {
     "ullsam_hyper_masks": [i32, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "ullsam_resize_bilinear": [vp, i64, i32, i32, i32, vp, vp, i32, i32, i32, f32, vp],
     "ullsam_mask_iou_counts": [vp, vp, vp, i32, i64, vp],
-    "ullsam_stability_score": [vp, i64, i64, f32, f32, vp, vp, vp],
+    "ullsam_stability_score": [vp, i64, i64, f64, f64, vp, vp, vp],
     "ullsam_mask_to_box": [vp, i64, i32, i32, vp, vp],
     "ullsam_rle_pack": [vp, i64, i32, i32, vp, vp, vp, vp],
     "ullsam_rle_emit": [vp, vp, i64, i32, i32, vp, vp, vp],
-    "ullsam_amg_postprocess": [vp, vp, i64] + [i32] * 11 + [f32, f32, vp, vp, vp, vp, vp, vp],
+    "ullsam_amg_postprocess": [vp, vp, i64] + [i32] * 11 + [f64, f64, vp, vp, vp, vp, vp, vp],
     "ullsam_nms_mask": [vp, i32, f32, vp, vp],
     "ullsam_threshold_u8": [vp, vp, i64, f32, vp],
     "ullsam_rle_to_mask": [vp, vp, i64, i32, i32, vp, vp, vp],

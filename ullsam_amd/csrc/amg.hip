@@ -24,15 +24,16 @@ __global__ void stability_finish_kernel(const unsigned int* __restrict__ counts,
     if (i < N) score[i] = (float)(int)counts[2 * i] / (float)(int)counts[2 * i + 1];  // int32 / int32 true division, as torch
 }
 
-// masks fp32 [N, per]; counts u32 [N,2] scratch (zeroed here); score fp32 [N]
-extern "C" int ullsam_stability_score(const float* masks, long N, long per, float mask_threshold, float threshold_offset,
+// masks fp32 [N, per]; counts u32 [N,2] scratch (zeroed here); score fp32 [N].  The thresholds arrive as doubles and are rounded ONCE, as the reference's
+// `masks > (mask_threshold + threshold_offset)` rounds the Python sum to the masks' float32: the sum of two floats differs for e.g. (-1.0, 0.6).
+extern "C" int ullsam_stability_score(const float* masks, long N, long per, double mask_threshold, double threshold_offset,
                                       unsigned int* counts, float* score, void* stream) {
     if (N == 0) return 0;
     ULLSAM_CHECK(((uintptr_t)masks & 15) == 0 && per % 4 == 0, "stability_score: masks must be 16-byte aligned, H*W %% 4 == 0");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (hipMemsetAsync(counts, 0, sizeof(unsigned int) * 2 * N, s) != hipSuccess) { ullsam_set_error("stability_score: memset failed"); return -2; }
     const int bx = (int)min((per / 4 + 255) / 256, (long)64);
-    stability_count_kernel<<<dim3(bx, (unsigned)N), 256, 0, s>>>(masks, per, mask_threshold + threshold_offset, mask_threshold - threshold_offset, counts);
+    stability_count_kernel<<<dim3(bx, (unsigned)N), 256, 0, s>>>(masks, per, (float)(mask_threshold + threshold_offset), (float)(mask_threshold - threshold_offset), counts);
     ULLSAM_LAUNCH_CHECK();
     stability_finish_kernel<<<(unsigned)((N + 255) / 256), 256, 0, s>>>(counts, score, N);
     ULLSAM_LAUNCH_CHECK();
@@ -322,7 +323,7 @@ __device__ __forceinline__ void push_gt(unsigned int& acc, float v, float thr) {
 // all of the block's bits without evaluating a pixel -- real masks are flat almost everywhere.
 template <int NC>
 __global__ __launch_bounds__(256) void amg_postprocess_kernel(const float* __restrict__ low, const int* __restrict__ index, PostGeom g,
-                                                              float thr, float off, unsigned long long* __restrict__ words,
+                                                              float thr, float hi, float lo, unsigned long long* __restrict__ words,
                                                               int* __restrict__ rle_counts, unsigned char* __restrict__ first,
                                                               int* __restrict__ boxes, unsigned int* __restrict__ stab) {
     const long n = blockIdx.z;
@@ -336,7 +337,6 @@ __global__ __launch_bounds__(256) void amg_postprocess_kernel(const float* __res
     const int xf0 = bx0 + lane * NC;                  // first frame column of the lane
     const int ys = yb * 64;
     const int r = min(64, g.FH - ys);                 // frame rows in this block
-    const float hi = thr + off, lo = thr - off;
     Tap tx[NC], t0[NC], t1[NC];
     bool col_in[NC];
 #pragma unroll
@@ -526,9 +526,10 @@ __global__ __launch_bounds__(256) void amg_postprocess_kernel(const float* __res
 
 // low f32 [*, LH, LW]; index int32 [M] rows of `low` to process (NULL = 0..M-1); S1 = Sam.image_encoder.img_size; (nh, nw) =
 // input_size; (CH, CW) = crop size; the crop sits at (cx0, cy0) of the FH x FW frame.  Outputs: words u64 [M, ceil(FH/64), FW],
-// rle_counts int [M], first u8 [M], boxes int [M,4] (crop coordinates, zeros when empty), stab u32 [M,2].
+// rle_counts int [M], first u8 [M], boxes int [M,4] (crop coordinates, zeros when empty), stab u32 [M,2].  The thresholds are doubles, rounded once
+// each (thr, thr + off, thr - off), as in ullsam_stability_score.
 extern "C" int ullsam_amg_postprocess(const float* low, const int* index, long M, int LH, int LW, int S1, int nh, int nw, int CH,
-                                      int CW, int FH, int FW, int cx0, int cy0, float mask_threshold, float threshold_offset,
+                                      int CW, int FH, int FW, int cx0, int cy0, double mask_threshold, double threshold_offset,
                                       unsigned long long* words, int* rle_counts, unsigned char* first, int* boxes,
                                       unsigned int* stab, void* stream) {
     if (M == 0) return 0;
@@ -546,12 +547,13 @@ extern "C" int ullsam_amg_postprocess(const float* low, const int* index, long M
     g.LH = LH; g.LW = LW; g.S1 = S1; g.nh = nh; g.nw = nw; g.CH = CH; g.CW = CW; g.FH = FH; g.FW = FW; g.cx0 = cx0; g.cy0 = cy0;
     g.s1y = (float)LH / (float)S1; g.s1x = (float)LW / (float)S1; g.s2y = (float)nh / (float)CH; g.s2x = (float)nw / (float)CW;
     const int nyb = (FH + 63) / 64;
+    const float thr = (float)mask_threshold, hi = (float)(mask_threshold + threshold_offset), lo = (float)(mask_threshold - threshold_offset);
     if (FW > 128)
         amg_postprocess_kernel<4><<<dim3((unsigned)((FW + 255) / 256), (unsigned)((nyb + 3) / 4), (unsigned)M), 256, 0, s>>>(
-            low, index, g, mask_threshold, threshold_offset, words, rle_counts, first, boxes, stab);
+            low, index, g, thr, hi, lo, words, rle_counts, first, boxes, stab);
     else
         amg_postprocess_kernel<1><<<dim3((unsigned)((FW + 63) / 64), (unsigned)((nyb + 3) / 4), (unsigned)M), 256, 0, s>>>(
-            low, index, g, mask_threshold, threshold_offset, words, rle_counts, first, boxes, stab);
+            low, index, g, thr, hi, lo, words, rle_counts, first, boxes, stab);
     ULLSAM_LAUNCH_CHECK();
     box_finish_kernel<<<(unsigned)((M + 255) / 256), 256, 0, s>>>(boxes, M);
     ULLSAM_LAUNCH_CHECK();
