@@ -736,6 +736,36 @@ int ullsam_measure_objects3d(const int* volume, int Z, int H, int W, int K, cons
 int ullsam_object_contacts3d(const int* volume, int Z, int H, int W, int K, unsigned long long* keys, long* counts, long cap, int max_pairs,
                              long* rows, int* flags, void* stream);
 
+/* Surface meshes and Euler numbers of a label VOLUME (csrc/mesh3d.hip; integer work, bit-exact with the host forms
+   utils.mesh3d.label_surfaces / object_topology, which drive these entries; definition in DESIGN.md "7b, continued (3-D surfaces)").  volume
+   i32 [Z, H, W] with ids 0..K, 0 = background, 1 <= Z, H, W <= 32767 and Z * H * W <= 2^31 - 1.  Voxel p = (z H + y) W + x has a face towards
+   d (0 = -z, 1 = +z, 2 = -y, 3 = +y, 4 = -x, 5 = +x) when its id k > 0 and the neighbour there is not k (the outside is not k); the face's id
+   is 6 p + d < 2^34, lattice corner (cx, cy, cz) has the id (cz (H + 1) + cy) (W + 1) + cx < 2^34, a key is id | label << 34 with
+   K <= 2^29 - 1 for the mesh entries.  flags i32 [4]: [0] = 1 when an id lies outside 0..K (it reads as background).
+   mesh3d_masks: masks u8 [Z, H, W] = the six face bits of every voxel (bit d; 0 on the background and for an id with only[id] == 0; only u8
+     [K + 1] or NULL = every id); a workgroup's tile is 64 x 4 x 4 voxels, tile_counts i32 [T] its faces, T = ceil(W / 64) ceil(H / 4)
+     ceil(Z / 4); tile_offsets i64 [T + 1] = their exclusive sums, [T] = F.
+   mesh3d_faces: fkeys u64 [F] = the face keys, a tile's at its offset (the caller sorts them).
+   mesh3d_corners: ckeys u64 [4 F] = the keys of the four corners of every face of fkeys, counter-clockwise seen from outside (the caller
+     sorts a copy).  mesh3d_heads: over n SORTED keys, 2048 a workgroup: block_counts i32 [B], B = ceil(n / 2048), = the keys that differ from
+     their predecessor, block_offsets i64 [B + 1] their exclusive sums, [B] = V.  mesh3d_vertices: ukeys u64 [V] = those keys in order,
+     vertices i32 [V, 3] = their (x, y, z).  mesh3d_quads: quads i32 [F, 4] = the index in ukeys of every corner key of fkeys (binary search).
+   mesh3d_starts: start i64 [K + 1], start[k] = the number of the n sorted keys whose label is <= k.
+   mesh3d_topology (K <= 2^31 - 2): euler i64 [K] = V - E + F - C of the cubical complex of id k's voxels (lattice corners, edges, faces
+     touched, voxels: components - tunnels + cavities under 26-connectivity), pinch_edges i64 [K] = the lattice edges whose four voxels are
+     k, not k, k, not k around the edge; both set here, 0 for an absent id. */
+int ullsam_mesh3d_masks(const int* volume, int Z, int H, int W, int K, const unsigned char* only, unsigned char* masks, int* tile_counts,
+                        long* tile_offsets, int* flags, void* stream);
+int ullsam_mesh3d_faces(const int* volume, const unsigned char* masks, int Z, int H, int W, const long* tile_offsets, unsigned long long* fkeys, long F,
+                        void* stream);
+int ullsam_mesh3d_corners(const unsigned long long* fkeys, long F, int H, int W, unsigned long long* ckeys, void* stream);
+int ullsam_mesh3d_heads(const unsigned long long* sorted, long n, int* block_counts, long* block_offsets, void* stream);
+int ullsam_mesh3d_vertices(const unsigned long long* sorted, long n, const long* block_offsets, int H, int W, unsigned long long* ukeys, int* vertices,
+                           long V, void* stream);
+int ullsam_mesh3d_quads(const unsigned long long* fkeys, long F, const unsigned long long* ukeys, long V, int H, int W, int* quads, void* stream);
+int ullsam_mesh3d_starts(const unsigned long long* sorted, long n, int K, long* start, void* stream);
+int ullsam_mesh3d_topology(const int* volume, int Z, int H, int W, int K, long* euler, long* pinch_edges, int* flags, void* stream);
+
 /* Point prompts, boxes and per-instance masks from one instance label image (csrc/prompts.hip; the reference's dataset loop
    train_joint_v2.py:313-468 as integer kernels, bit-exact with utils.prompts' host route; definitions in DESIGN.md "7b, continued (prompts)").
    labels i32 [H, W], 0 = background, ids 1..65535; H * W < 2^31; radius, hi <= 64; num_pos, num_neg <= 16.

@@ -61,6 +61,10 @@ HOT_DISTANCE3D = [r"dist3_z_kernelILb[01]E", r"dist3_y_kernelILb[01]E", r"dist3_
 HOT_SPLIT3D = [r"split3_ascent_kernelILb[01]E", r"split3_passes_kernel", r"split3_tables_kernel", r"split3_relabel_kernel"]
 # per-object measurements and contacts from a label volume (csrc/measure3d.hip): the tile kernel for 0..4 channels, the contacts, init and compaction
 HOT_MEASURE3D = [r"measure3d_kernelILi\dE", r"contacts3d_kernel", r"measure3d_init_kernel", r"contacts3d_init_kernel", r"contacts3d_compact_kernel"]
+# surface meshes and Euler numbers of a label volume (csrc/mesh3d.hip): face masks, the one-workgroup scan, face keys,
+# corner keys, the heads of the sorted corner keys counted and written, quad indices, per-id offsets, init, topology.  A list of its own: it is in no aggregate.
+HOT_MESH3D = [r"mesh3d_mask_kernel", r"mesh3d_scan_kernel", r"mesh3d_faces_kernel", r"mesh3d_corners_kernel", r"mesh3d_heads_kernelILb[01]E",
+              r"mesh3d_quads_kernel", r"mesh3d_starts_kernel", r"mesh3d_init_kernel", r"mesh3d_topology_kernel"]
 HOT_BF16 = (HOT_BF16 + HOT_AMG + HOT_REGIONS + HOT_DECODE_FP8 + HOT_LABELS + HOT_MEASURE + HOT_DISTANCE + HOT_SPLIT + HOT_OUTLINE + HOT_RASTER
             + HOT_DISTANCE3D + HOT_SPLIT3D + HOT_MEASURE3D)
 HOT = HOT_BF16

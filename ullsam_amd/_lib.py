@@ -156,6 +156,14 @@ SIGNATURES = {
     "ullsam_label_contacts": [vp, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp],
     "ullsam_measure_objects3d": [vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "ullsam_object_contacts3d": [vp, i32, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp],
+    "ullsam_mesh3d_masks": [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+    "ullsam_mesh3d_faces": [vp, vp, i32, i32, i32, vp, vp, i64, vp],
+    "ullsam_mesh3d_corners": [vp, i64, i32, i32, vp, vp],
+    "ullsam_mesh3d_heads": [vp, i64, vp, vp, vp],
+    "ullsam_mesh3d_vertices": [vp, i64, vp, i32, i32, vp, vp, i64, vp],
+    "ullsam_mesh3d_quads": [vp, i64, vp, i64, i32, i32, vp, vp],
+    "ullsam_mesh3d_starts": [vp, i64, i32, vp, vp],
+    "ullsam_mesh3d_topology": [vp, i32, i32, i32, i32, vp, vp, vp, vp],
     "ullsam_label_d1": [vp, i32, i32, i32, vp, vp, vp, vp],
     "ullsam_prompt_choose": [vp, i32, C.c_ulonglong, vp, vp, vp, vp, vp],
     "ullsam_prompt_sets": [vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],

@@ -2159,6 +2159,155 @@ def object_contacts3d(volume: torch.Tensor, num: int, max_pairs: int = 1 << 20, 
     return rows, flags
 
 
+# ---- surface meshes and Euler numbers of a label volume (csrc/mesh3d.hip; utils.mesh3d drives these) -------------------------------------------
+MESH3D_TILE_Y = 4                     # MS_TILE_Y and MS_TILE_Z of csrc/mesh3d.hip: a workgroup's tile is 64 columns x 4 rows x 4 planes
+MESH3D_TILE_Z = 4
+MESH3D_TILE_X = 64
+MESH3D_MAX_LABEL = 2 ** 29 - 1        # a key is id | label << 34 and stays below 2^63
+MESH3D_KEY_SHIFT = 34
+INT32_MAX_COUNT = 2 ** 31 - 1         # faces and vertices are indexed in int32
+MESH3D_BLOCK_KEYS = 2048              # sorted keys per workgroup of the heads / vertices kernels
+
+
+def _mesh3d_volume(volume: torch.Tensor, num: int, what: str, max_label: int):
+    _chk(volume, "volume", torch.int32)
+    if volume.dim() != 3:
+        raise ValueError(f"{what}: volume must be [Z, H, W], got {tuple(volume.shape)}")
+    z, h, w = volume.shape
+    if not all(1 <= n <= MEASURE3D_MAX_SIDE for n in (z, h, w)) or z * h * w > MEASURE3D_MAX_VOXELS:
+        raise _lib.UllsamError(f"{what}: a volume of {z} x {h} x {w} (each side in 1..{MEASURE3D_MAX_SIDE}, at most 2^31 - 1 voxels)")
+    if not 0 <= int(num) <= max_label:
+        raise _lib.UllsamError(f"{what}: num = {num} must lie in 0..{max_label}")
+    return z, h, w
+
+
+def _mesh3d_keys(t: torch.Tensor, name: str) -> int:
+    _chk(t, name, torch.int64)
+    if t.dim() != 1 or t.numel() > 4 * INT32_MAX_COUNT:
+        raise ValueError(f"{name} must be int64 [n] with n <= 4 (2^31 - 1), got {tuple(t.shape)}")
+    return t.numel()
+
+
+def _mesh3d_plane(h: int, w: int, what: str):
+    h, w = int(h), int(w)
+    if not (1 <= h <= MEASURE3D_MAX_SIDE and 1 <= w <= MEASURE3D_MAX_SIDE):
+        raise _lib.UllsamError(f"{what}: H = {h} and W = {w} must lie in 1..{MEASURE3D_MAX_SIDE}")
+    return h, w
+
+
+def mesh3d_tiles(z: int, h: int, w: int) -> int:
+    return -(-w // MESH3D_TILE_X) * -(-h // MESH3D_TILE_Y) * -(-z // MESH3D_TILE_Z)
+
+
+def mesh3d_masks(volume: torch.Tensor, num: int, only: Optional[torch.Tensor] = None, flags: Optional[torch.Tensor] = None):
+    """volume int32 [Z, H, W] with ids 0..num <= 2^29 - 1, only None or uint8 [num + 1] (faces are made for the ids with only[id] != 0) -> (masks uint8
+    [Z, H, W]: bit d of a voxel = it has a face towards d (0 = -z, 1 = +z, 2 = -y, 3 = +y, 4 = -x, 5 = +x); tile_offsets int64 [T + 1]: the exclusive
+    sums of the faces per 64 x 4 x 4 tile, [T] = F; flags int32 [4]: the caller reads flags[0])."""
+    z, h, w = _mesh3d_volume(volume, num, "mesh3d_masks", MESH3D_MAX_LABEL)
+    if only is not None:
+        _chk(only, "only", torch.uint8)
+        if tuple(only.shape) != (int(num) + 1,):
+            raise ValueError(f"mesh3d_masks: only must be uint8 [num + 1] = [{int(num) + 1}], got {tuple(only.shape)}")
+    dev, t = volume.device, mesh3d_tiles(z, h, w)
+    masks = torch.empty((z, h, w), dtype=torch.uint8, device=dev)
+    counts = torch.empty((t,), dtype=torch.int32, device=dev)
+    offsets = torch.empty((t + 1,), dtype=torch.int64, device=dev)
+    flags = _out_i32(flags, (MEASURE_FLAGS,), dev, "flags")
+    _lib.call("ullsam_mesh3d_masks", volume.data_ptr(), z, h, w, int(num), _p(only), masks.data_ptr(), counts.data_ptr(), offsets.data_ptr(),
+              flags.data_ptr(), _stream())
+    return masks, offsets, flags
+
+
+def mesh3d_faces(volume: torch.Tensor, masks: torch.Tensor, tile_offsets: torch.Tensor, faces: int) -> torch.Tensor:
+    """masks, tile_offsets of mesh3d_masks and faces = F = tile_offsets[-1] -> fkeys int64 [F] = 6 p + d | label << 34 of every face, a tile's at
+    its offset (not sorted)."""
+    z, h, w = _mesh3d_volume(volume, 0, "mesh3d_faces", MESH3D_MAX_LABEL)
+    _chk(masks, "masks", torch.uint8); _chk(tile_offsets, "tile_offsets", torch.int64)
+    if tuple(masks.shape) != (z, h, w) or tuple(tile_offsets.shape) != (mesh3d_tiles(z, h, w) + 1,):
+        raise ValueError(f"mesh3d_faces: masks {tuple(masks.shape)} / tile_offsets {tuple(tile_offsets.shape)} for a volume {(z, h, w)}")
+    f = int(faces)
+    if not 0 <= f <= INT32_MAX_COUNT:
+        raise _lib.UllsamError(f"mesh3d_faces: {f} faces (at most 2^31 - 1)")
+    fkeys = torch.empty((f,), dtype=torch.int64, device=volume.device)
+    _lib.call("ullsam_mesh3d_faces", volume.data_ptr(), masks.data_ptr(), z, h, w, tile_offsets.data_ptr(), fkeys.data_ptr(), f, _stream())
+    return fkeys
+
+
+def mesh3d_corners(fkeys: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """fkeys int64 [F] -> ckeys int64 [4 F]: corner id | label << 34 of the four corners of every face, counter-clockwise seen from outside."""
+    f = _mesh3d_keys(fkeys, "fkeys")
+    h, w = _mesh3d_plane(h, w, "mesh3d_corners")
+    if f > INT32_MAX_COUNT:
+        raise _lib.UllsamError(f"mesh3d_corners: {f} faces (at most 2^31 - 1)")
+    ckeys = torch.empty((4 * f,), dtype=torch.int64, device=fkeys.device)
+    _lib.call("ullsam_mesh3d_corners", fkeys.data_ptr(), f, h, w, ckeys.data_ptr(), _stream())
+    return ckeys
+
+
+def mesh3d_heads(sorted_keys: torch.Tensor) -> torch.Tensor:
+    """sorted int64 [n] -> block_offsets int64 [B + 1], B = ceil(n / 2048): the exclusive sums of the number of keys per block that differ from their
+    predecessor; [B] = the number of distinct keys."""
+    n = _mesh3d_keys(sorted_keys, "sorted_keys")
+    b = -(-n // MESH3D_BLOCK_KEYS)
+    counts = torch.empty((max(b, 1),), dtype=torch.int32, device=sorted_keys.device)
+    offsets = torch.empty((b + 1,), dtype=torch.int64, device=sorted_keys.device)
+    _lib.call("ullsam_mesh3d_heads", sorted_keys.data_ptr(), n, counts.data_ptr(), offsets.data_ptr(), _stream())
+    return offsets
+
+
+def mesh3d_vertices(sorted_keys: torch.Tensor, block_offsets: torch.Tensor, count: int, h: int, w: int, vertices: Optional[torch.Tensor] = None):
+    """sorted corner keys, mesh3d_heads' offsets and count = V = block_offsets[-1] -> (ukeys int64 [V] = the distinct keys in order, vertices int32
+    [V, 3] = their lattice corners (x, y, z))."""
+    n = _mesh3d_keys(sorted_keys, "sorted_keys")
+    h, w = _mesh3d_plane(h, w, "mesh3d_vertices")
+    _chk(block_offsets, "block_offsets", torch.int64)
+    if tuple(block_offsets.shape) != (-(-n // MESH3D_BLOCK_KEYS) + 1,):
+        raise ValueError(f"mesh3d_vertices: block_offsets {tuple(block_offsets.shape)} for {n} keys")
+    v = int(count)
+    if not 0 <= v <= min(n, INT32_MAX_COUNT):
+        raise _lib.UllsamError(f"mesh3d_vertices: {v} vertices of {n} keys (at most 2^31 - 1)")
+    ukeys = torch.empty((v,), dtype=torch.int64, device=sorted_keys.device)
+    vertices = _out_i32(vertices, (v, 3), sorted_keys.device, "vertices")
+    _lib.call("ullsam_mesh3d_vertices", sorted_keys.data_ptr(), n, block_offsets.data_ptr(), h, w, ukeys.data_ptr(), vertices.data_ptr(), v, _stream())
+    return ukeys, vertices
+
+
+def mesh3d_quads(fkeys: torch.Tensor, ukeys: torch.Tensor, h: int, w: int, quads: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fkeys int64 [F], ukeys int64 [V] sorted and distinct -> quads int32 [F, 4]: the index in ukeys of each corner key of each face."""
+    f, v = _mesh3d_keys(fkeys, "fkeys"), _mesh3d_keys(ukeys, "ukeys")
+    h, w = _mesh3d_plane(h, w, "mesh3d_quads")
+    if f > INT32_MAX_COUNT or v > INT32_MAX_COUNT:
+        raise _lib.UllsamError(f"mesh3d_quads: {f} faces and {v} vertices (at most 2^31 - 1 each)")
+    quads = _out_i32(quads, (f, 4), fkeys.device, "quads")
+    _lib.call("ullsam_mesh3d_quads", fkeys.data_ptr(), f, ukeys.data_ptr(), v, h, w, quads.data_ptr(), _stream())
+    return quads
+
+
+def mesh3d_starts(sorted_keys: torch.Tensor, num: int, start: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sorted int64 [n] -> start int64 [num + 1]: start[k] = the number of keys whose label (key >> 34) is <= k."""
+    n, k = _mesh3d_keys(sorted_keys, "sorted_keys"), int(num)
+    if not 0 <= k <= MESH3D_MAX_LABEL:
+        raise _lib.UllsamError(f"mesh3d_starts: num = {k} must lie in 0..2^29 - 1")
+    if start is None:
+        start = torch.empty((k + 1,), dtype=torch.int64, device=sorted_keys.device)
+    _chk(start, "start", torch.int64)
+    assert tuple(start.shape) == (k + 1,), (tuple(start.shape), k + 1)
+    _lib.call("ullsam_mesh3d_starts", sorted_keys.data_ptr(), n, k, start.data_ptr(), _stream())
+    return start
+
+
+def mesh3d_topology(volume: torch.Tensor, num: int, out: Optional[dict] = None, flags: Optional[torch.Tensor] = None):
+    """volume int32 [Z, H, W] with ids 0..num -> (euler int64 [num], pinch_edges int64 [num], flags int32 [4]: the caller reads flags[0]); the
+    definitions of ullsam_hip.h.  out: preallocated tables by name."""
+    z, h, w = _mesh3d_volume(volume, num, "mesh3d_topology", MOSAIC_MAX_IDS)
+    k, dev = int(num), volume.device
+    euler = _out_view(out, "euler", (k,), torch.int64, dev)
+    pinch = _out_view(out, "pinch_edges", (k,), torch.int64, dev)
+    flags = _out_i32(flags, (MEASURE_FLAGS,), dev, "flags")
+    _lib.call("ullsam_mesh3d_topology", volume.data_ptr(), z, h, w, k, euler.data_ptr(), pinch.data_ptr(), flags.data_ptr(), _stream())
+    return euler, pinch, flags
+
+
 # ---- the interactive loop's display tail (csrc/interactive.hip) ---------------------------------------------------------------------
 CLICK_MAX_P = 512
 
