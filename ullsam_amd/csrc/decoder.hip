@@ -31,6 +31,7 @@ __global__ __launch_bounds__(256) void small_linear_kernel(const float* __restri
 extern "C" int ullsam_small_linear(const float* x, long ldx, const float* W, const float* b, const float* res, long ldr, float* y,
                                    long ldy, int M, int N, int K, int act, void* stream) {
     ULLSAM_CHECK(K % 4 == 0 && ldx % 4 == 0, "small_linear: K and ldx must be multiples of 4");
+    ULLSAM_CHECK((((uintptr_t)x | (uintptr_t)W) & 15) == 0, "small_linear: x and W must be 16-byte aligned");
     const long outs = (long)M * N;
     if (outs == 0) return 0;
     small_linear_kernel<<<(unsigned)((outs + 3) / 4), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(x, ldx, W, b, res, ldr, y, ldy, M, N, K, act);
@@ -159,6 +160,8 @@ extern "C" int ullsam_set_skinny_linear_mfma(int on) { const int old = g_skinny_
 extern "C" int ullsam_skinny_linear(const float* x, long ldx, const float* WT, const float* b, const float* res, long ldr, float* y,
                                     long ldy, int M, int N, int K, int act, void* stream) {
     ULLSAM_CHECK(K % 128 == 0 && ldx % 4 == 0 && ((uintptr_t)x & 15) == 0, "skinny_linear: K %% 128, ldx %% 4, 16-byte aligned x");
+    ULLSAM_CHECK(M >= 0 && N >= 0 && K > 0, "skinny_linear: M=%d, N=%d must not be negative and K=%d must be positive", M, N, K);
+    ULLSAM_CHECK(ldy >= N && (!res || ldr >= N), "skinny_linear: ldy=%ld (and ldr=%ld with a residual) must be >= N=%d", ldy, ldr, N);
     if ((long)M * N == 0) return 0;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // (K >= 1024: sixteen waves split K -- with four a wave's share is a chain of 256 dependent MFMAs, 179 us per launch at K = 2048)

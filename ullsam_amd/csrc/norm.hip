@@ -289,6 +289,17 @@ extern "C" int ullsam_norm_fanout(const float* in, long rows, int D, const float
     return 0;
 }
 
+// what the kernels take for granted (16-byte loads and stores of 4 elements, rows that do not overlap); after the rows == 0 return, so an empty call may pass nulls
+static int norm_operands_ok(const char* who, const void* in, int in_dtype, long in_stride, const void* out, int out_dtype, long out_stride, const float* w,
+                            const float* b, int D) {
+    ULLSAM_CHECK(in && out, "%s: null argument", who);
+    ULLSAM_CHECK(in_stride >= D && out_stride >= D, "%s: strides (%ld, %ld) must be >= D=%d", who, in_stride, out_stride, D);
+    ULLSAM_CHECK(((uintptr_t)in & (in_dtype == 0 ? 15 : 7)) == 0 && ((uintptr_t)out & (out_dtype == 0 ? 15 : 7)) == 0,
+                 "%s: input and output must be aligned to 4 elements (16 bytes fp32, 8 bytes bf16)", who);
+    ULLSAM_CHECK((((uintptr_t)w | (uintptr_t)b) & 15) == 0, "%s: weight and bias must be 16-byte aligned", who);
+    return 0;
+}
+
 // in_dtype/out_dtype: 0 f32, 1 bf16.  w/b may be null.  rms=1 -> RMSNorm (b ignored).
 extern "C" int ullsam_norm(const void* in, int in_dtype, long in_stride, void* out, int out_dtype, long out_stride,
                            const float* w, const float* b, long rows, int D, float eps, int rms, int act,
@@ -297,6 +308,8 @@ extern "C" int ullsam_norm(const void* in, int in_dtype, long in_stride, void* o
     ULLSAM_CHECK(rows >= 0, "ullsam_norm: bad rows");
     if (rows == 0) return 0;
     ULLSAM_CHECK(in_stride % 4 == 0 && out_stride % 4 == 0, "ullsam_norm: strides must be multiples of 4 elements");
+    ULLSAM_CHECK((in_dtype == 0 || in_dtype == 1) && (out_dtype == 0 || out_dtype == 1), "ullsam_norm: bad dtypes %d %d", in_dtype, out_dtype);
+    if (norm_operands_ok("ullsam_norm", in, in_dtype, in_stride, out, out_dtype, out_stride, w, rms ? nullptr : b, D)) return -1;
     NormArgs a{in, out, w, rms ? nullptr : b, rows, D, in_stride, out_stride, eps, rms, act, post_scale, post_shift, 0};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (in_dtype == 0 && out_dtype == 0) return launch_norm<float, float>(a, s);
@@ -314,6 +327,8 @@ extern "C" int ullsam_norm_panels(const void* in, int in_dtype, long in_stride, 
     ULLSAM_CHECK(rows >= 0 && in_stride % 4 == 0, "ullsam_norm_panels: bad rows / input stride");
     ULLSAM_CHECK(!out_panels || (D % 32 == 0 && ((uintptr_t)out & 1023) == 0), "ullsam_norm_panels: panels need D %% 32 == 0 and a 1 KiB aligned output (D=%d)", D);
     if (rows == 0) return 0;
+    ULLSAM_CHECK(in_dtype == 0 || in_dtype == 1, "ullsam_norm_panels: bad input dtype %d", in_dtype);
+    if (norm_operands_ok("ullsam_norm_panels", in, in_dtype, in_stride, out, 1, (long)D, w, rms ? nullptr : b, D)) return -1;
     NormArgs a{in, out, w, rms ? nullptr : b, rows, D, in_stride, (long)D, eps, rms, act, post_scale, post_shift, out_panels != 0};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (in_dtype == 0) return launch_norm<float, bf16>(a, s);
@@ -389,10 +404,14 @@ __global__ __launch_bounds__(256) void rows_fp8_kernel(const TI* __restrict__ in
 // w / b non-null: LayerNorm(eps) first (image_encoder.py:166,180), else plain quantisation (weights).
 extern "C" int ullsam_rows_fp8(const void* in, int in_dtype, long in_stride, void* out, long out_stride, float* scale, const float* w,
                                const float* b, long rows, int D, float eps, void* stream) {
-    ULLSAM_CHECK(D % 4 == 0 && D <= 8192 && rows >= 0, "ullsam_rows_fp8: D=%d must be a multiple of 4, <= 8192", D);
+    ULLSAM_CHECK(in_dtype == ULLSAM_DT_F32 || in_dtype == ULLSAM_DT_BF16, "ullsam_rows_fp8: bad dtype %d", in_dtype);
+    ULLSAM_CHECK(D > 0 && D % 4 == 0 && D <= 8192 && rows >= 0, "ullsam_rows_fp8: D=%d must be a positive multiple of 4, <= 8192", D);
     ULLSAM_CHECK((w == nullptr) == (b == nullptr), "ullsam_rows_fp8: weight and bias go together");
-    ULLSAM_CHECK(out_stride % 4 == 0 && ((uintptr_t)out & 3) == 0, "ullsam_rows_fp8: output rows must be 4-byte aligned");
+    ULLSAM_CHECK((((uintptr_t)w | (uintptr_t)b) & 15) == 0, "ullsam_rows_fp8: weight and bias must be 16-byte aligned");
+    ULLSAM_CHECK(in_stride >= D && in_stride % 4 == 0 && ((uintptr_t)in & (in_dtype == ULLSAM_DT_F32 ? 15 : 7)) == 0, "ullsam_rows_fp8: input rows must be aligned groups of 4 elements");
+    ULLSAM_CHECK(out_stride >= D && out_stride % 4 == 0 && ((uintptr_t)out & 3) == 0, "ullsam_rows_fp8: output rows must be 4-byte aligned");
     if (rows == 0) return 0;
+    ULLSAM_CHECK(in && out && scale, "ullsam_rows_fp8: null argument");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((rows + 3) / 4));
     const int nv = D / 4, maxv = (nv + 63) / 64;
