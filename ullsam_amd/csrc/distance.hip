@@ -22,7 +22,7 @@
 // pixel: a 64-bit atomicMax of D2 << 32 | (0xFFFFFFFF - linear index), sent only when a relaxed load says it improves -- the largest D2 and, among
 // its pixels, the first in row-major order whatever the order of arrival.
 // flags[0] = 1 when a label is negative or above K (the pixel is skipped; no table is indexed with it).
-#include "pair_table.h"   // the relaxed atomics
+#include "label_common.h"   // the relaxed atomics, isqrt_floor
 #include <limits.h>
 #include <stdint.h>
 
@@ -151,9 +151,7 @@ __global__ __launch_bounds__(DT_TILE) void dist_rows_kernel(const int* __restric
         if (MODE == DT_SHRINK) out0[row + x] = bd > limit ? l : 0;
         if (MODE == DT_DEPTH) {
             const mz_u64 word = ((mz_u64)bd << 32) | (mz_u64)(0xFFFFFFFFu - (unsigned)(row + x));
-            mz_u64* slot = best + (l - 1);
-            if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < word)
-                (void)__hip_atomic_fetch_max(slot, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            mz_send_max(best + (l - 1), word);
         }
     } else {
         if (l < 0 || l > K) mz_store(flags + 0, 1);
@@ -203,13 +201,6 @@ __global__ __launch_bounds__(256) void dist_depth_decode_kernel(const mz_u64* __
 #define DT_FRAME_CHECK(what) \
     ULLSAM_CHECK(H >= 1 && H <= 32767 && W >= 1 && W <= 32767 && K >= 0 && K <= 2147483647L, what ": need 1 <= H, W <= 32767 and 0 <= K <= 2^31 - 1")
 
-static int dt_isqrt(long v) {                            // floor(sqrt(v)), 0 <= v < 2^31
-    int r = 0;
-    for (int bit = 1 << 15; bit; bit >>= 1)
-        if ((long)(r + bit) * (r + bit) <= v) r += bit;
-    return r;
-}
-
 extern "C" int ullsam_distance_columns(const int* labels, int H, int W, int feature, int edge, long K, unsigned short* g, int* nearest, int* flags,
                                        void* stream) {
     DT_FRAME_CHECK("distance_columns");
@@ -239,11 +230,11 @@ extern "C" int ullsam_distance_rows(const int* labels, const unsigned short* g, 
     ULLSAM_CHECK((mode != DT_INNER && mode != DT_DEPTH) || limit == 2147483647L, "distance_rows: the distance map and the depths are unbounded (limit = 2^31 - 1)");
     ULLSAM_CHECK(mode == DT_DEPTH ? (best != nullptr || K == 0) : out0 != nullptr, "distance_rows: the mode's output is missing");
     ULLSAM_CHECK(mode != DT_FEATURE || out1 != nullptr, "distance_rows: the feature pair has two outputs");
-    const int maxdx = limit == 2147483647L ? W : min(dt_isqrt(limit), W);
+    const int maxdx = limit == 2147483647L ? W : min(isqrt_floor(limit), W);
     ULLSAM_CHECK(route != 1 || maxdx <= DT_HALO, "distance_rows: the LDS route holds a halo of at most 128 columns");
     const bool lds = route == 1 || (route == 0 && maxdx <= DT_HALO);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (mode == DT_DEPTH && K > 0 && hipMemsetAsync(best, 0, (size_t)K * 8, s) != hipSuccess) {
+    if (mode == DT_DEPTH && !mz_zero(best, (size_t)K * 8, s)) {
         ullsam_set_error("distance_rows: memset failed");
         return -2;
     }
@@ -264,7 +255,7 @@ extern "C" int ullsam_distance_rows(const int* labels, const unsigned short* g, 
 extern "C" int ullsam_distance_depth_decode(const unsigned long long* best, long K, int W, int* r2, int* xy, void* stream) {
     ULLSAM_CHECK(K >= 0 && K <= 2147483646L && W >= 1 && W <= 32767, "distance_depth_decode: need 0 <= K <= 2^31 - 2 and 1 <= W <= 32767");
     if (K == 0) return 0;
-    dist_depth_decode_kernel<<<(unsigned)((K + 255) / 256), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(reinterpret_cast<const mz_u64*>(best), K, W, r2,
+    dist_depth_decode_kernel<<<mz_blocks(K), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(reinterpret_cast<const mz_u64*>(best), K, W, r2,
                                                                                                            xy);
     ULLSAM_LAUNCH_CHECK();
     return 0;

@@ -23,7 +23,7 @@
 // Arithmetic: the host bounds B = sum over the axes of s_a^2 (n_a - 1 + e_a)^2 by 2^31 - 2, so every w d^2 the loops form and every finite g^2,
 // h is at most B; a sum of two such terms is formed in unsigned 32 bits (< 2^32) and "none" is skipped before adding.
 // flags[0] = 1 when a label is negative or above K (the voxel is skipped; no table is indexed with it).
-#include "pair_table.h"   // the relaxed atomics
+#include "label_common.h"   // the relaxed atomics, isqrt_floor
 #include <limits.h>
 #include <stdint.h>
 
@@ -199,9 +199,7 @@ __global__ __launch_bounds__(D3_TILE) void dist3_x_kernel(const int* __restrict_
         if (MODE == D3_SHRINK) out0[row + x] = bd > limit ? l : 0;
         if (MODE == D3_DEPTH) {
             const mz_u64 word = ((mz_u64)bd << 32) | (mz_u64)(0xFFFFFFFFu - (unsigned)(row + x));
-            mz_u64* slot = best + (l - 1);
-            if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < word)
-                (void)__hip_atomic_fetch_max(slot, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            mz_send_max(best + (l - 1), word);
         }
     } else {
         if (l < 0 || l > K) mz_store(flags + 0, 1);
@@ -271,17 +269,10 @@ static bool d3_metric_ok(int Z, int H, int W, int sz, int sy, int sx, int ez, in
 #define D3_METRIC_CHECK(what) \
     ULLSAM_CHECK(d3_metric_ok(Z, H, W, sz, sy, sx, ez, ey, ex), what ": need 1 <= s <= 46340 and sum of s_a^2 (n_a - 1 + e_a)^2 <= 2^31 - 2")
 
-static int d3_isqrt(long v) {                            // floor(sqrt(v)), 0 <= v < 2^31
-    int r = 0;
-    for (int bit = 1 << 15; bit; bit >>= 1)
-        if ((long)(r + bit) * (r + bit) <= v) r += bit;
-    return r;
-}
-
 // the farthest step of a scan along an axis of n voxels at spacing s: the whole line, or floor(sqrt(limit) / s) = isqrt(limit / s^2) when bounded
 static int d3_reach(int n, int s, int e, long limit) {
     const int whole = n - 1 + (e ? 1 : 0);
-    return limit == 2147483647L ? whole : min(d3_isqrt(limit / ((long)s * s)), whole);
+    return limit == 2147483647L ? whole : min(isqrt_floor(limit / ((long)s * s)), whole);
 }
 
 extern "C" int ullsam_distance3d_z(const int* volume, int Z, int H, int W, int feature, int ez, long K, unsigned short* g, int* nearest, int* flags,
@@ -328,7 +319,7 @@ extern "C" int ullsam_distance3d_x(const int* volume, const int* h, const int* h
     ULLSAM_CHECK(mode != D3_FEATURE || out1 != nullptr, "distance3d_x: the feature pair has two outputs");
     const int maxd = d3_reach(W, sx, ex, limit);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (mode == D3_DEPTH && K > 0 && hipMemsetAsync(best, 0, (size_t)K * 8, s) != hipSuccess) {
+    if (mode == D3_DEPTH && !mz_zero(best, (size_t)K * 8, s)) {
         ullsam_set_error("distance3d_x: memset failed");
         return -2;
     }
@@ -350,7 +341,7 @@ extern "C" int ullsam_distance3d_depth_decode(const unsigned long long* best, lo
     ULLSAM_CHECK(K >= 0 && K <= 2147483646L && H >= 1 && H <= 32767 && W >= 1 && W <= 32767,
                  "distance3d_depth_decode: need 0 <= K <= 2^31 - 2 and 1 <= H, W <= 32767");
     if (K == 0) return 0;
-    dist3_depth_decode_kernel<<<(unsigned)((K + 255) / 256), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(reinterpret_cast<const mz_u64*>(best), K, H,
+    dist3_depth_decode_kernel<<<mz_blocks(K), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(reinterpret_cast<const mz_u64*>(best), K, H,
                                                                                                             W, r2, xyz);
     ULLSAM_LAUNCH_CHECK();
     return 0;

@@ -20,13 +20,8 @@
 // Compaction.  One workgroup: the dropped decision, an exclusive scan of the kept flags over the (at most 65535) ranks, the table
 // raw label -> final label, label_of_record, the kept labels' areas / boxes, and K.
 // Remap.  labels[y, x] = map[rawT[x, y]] through a 32 x 33 LDS tile: coalesced reads of the scratch, coalesced writes of the image.
-#include "common.h"
+#include "label_common.h"   // the relaxed atomics, the memset helper
 #include <limits.h>
-
-__device__ __forceinline__ int lb_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void lb_max(int* p, int v) { (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void lb_min(int* p, int v) { (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void lb_add(int* p, int v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---- paint ------------------------------------------------------------------------------------------------------------------
 #define LP_PT 8
@@ -62,7 +57,7 @@ __global__ __launch_bounds__(256) void rle_paint_kernel(const int* __restrict__ 
             loc[j] = tsum;
             tsum += c;
         }
-        long inc = tsum;                                 // inclusive wave scan of the threads' sums
+        long inc = tsum;                                 // inclusive wave scan of the threads' sums (written out: wave_scan_incl() changes this kernel's code)
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const long u = __shfl_up(inc, o, 64);
@@ -84,7 +79,7 @@ __global__ __launch_bounds__(256) void rle_paint_kernel(const int* __restrict__ 
             const long len = (j + 1 < LP_PT ? before + loc[j + 1] : before + tsum) - f0;
             if (len > 0 && len <= LP_LONG && f0 < per) {
                 const long fe = min(f0 + len, per);
-                for (long f = f0; f < fe; ++f) lb_max(rawT + f, value);
+                for (long f = f0; f < fe; ++f) mz_max(rawT + f, value);
             }
         }
         // long 1-runs: a wave each, lanes over consecutive f
@@ -93,7 +88,7 @@ __global__ __launch_bounds__(256) void rle_paint_kernel(const int* __restrict__ 
             const long len = start[r + 1] - f0;
             if (len <= LP_LONG || f0 >= per) continue;   // wave-uniform
             const long fe = min(f0 + len, per);
-            for (long f = f0 + lane; f < fe; f += 64) lb_max(rawT + f, value);
+            for (long f = f0 + lane; f < fe; f += 64) mz_max(rawT + f, value);
         }
         carry = start[LP_CH];
     }
@@ -117,7 +112,7 @@ __global__ __launch_bounds__(256) void label_stats_init_kernel(long N, int* __re
 
 // a run of label v (1..N) over the flat transposed range [f0, f0 + cnt)
 __device__ __forceinline__ void lb_run(int v, long f0, int cnt, int H, int* __restrict__ areas, int* __restrict__ boxes) {
-    lb_add(areas + v, cnt);
+    mz_add(areas + v, cnt);
     const unsigned int a = (unsigned int)f0, b = (unsigned int)(f0 + cnt - 1);
     const int x0 = (int)(a / (unsigned int)H), x1 = (int)(b / (unsigned int)H);
     int y0 = 0, y1 = H - 1;
@@ -126,10 +121,10 @@ __device__ __forceinline__ void lb_run(int v, long f0, int cnt, int H, int* __re
         y1 = (int)(b - (unsigned int)x1 * (unsigned int)H);
     }
     int* bx = boxes + 4 * (long)v;
-    if (lb_load(bx + 0) > x0) lb_min(bx + 0, x0);
-    if (lb_load(bx + 1) > y0) lb_min(bx + 1, y0);
-    if (lb_load(bx + 2) < x1) lb_max(bx + 2, x1);
-    if (lb_load(bx + 3) < y1) lb_max(bx + 3, y1);
+    mz_send_min(bx + 0, x0);
+    mz_send_min(bx + 1, y0);
+    mz_send_max(bx + 2, x1);
+    mz_send_max(bx + 3, y1);
 }
 
 __global__ __launch_bounds__(256) void label_stats_kernel(const int* __restrict__ rawT, long per, int N, int H, int* __restrict__ areas,
@@ -212,7 +207,7 @@ __global__ __launch_bounds__(256) void label_compact_kernel(const int* __restric
     __syncthreads();                                     // map[] is read below by other threads of this workgroup
     for (int i = t; i < N; i += 256) {
         const int rk = rank[i];
-        label_of_record[i] = (rk >= 0 && rk < N) ? lb_load(map + rk + 1) : 0;
+        label_of_record[i] = (rk >= 0 && rk < N) ? mz_load(map + rk + 1) : 0;
     }
 }
 
@@ -242,9 +237,6 @@ __global__ __launch_bounds__(256) void label_remap_kernel(const int* __restrict_
 }
 
 // ---- overlap table ----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void lb_add64(unsigned long long* p, unsigned long long v) {
-    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 // T[a, b] += the length of every run of equal (a, b) pairs of a 64-pixel segment of the flat images (a count does not care where a row
 // ends), one add per wave for a run of whole segments: the background / background pair of two 2048^2 images costs 2048 adds, not 4 M.
 __global__ __launch_bounds__(256) void label_overlap_kernel(const int* __restrict__ A, const int* __restrict__ B, long per, int na, int nb,
@@ -272,21 +264,21 @@ __global__ __launch_bounds__(256) void label_overlap_kernel(const int* __restric
             const long c0 = __shfl(cell, 0, 64);
             if (c0 == cur) cnt += 64;
             else {
-                if (cur >= 0 && lane == 0) lb_add64(T + cur, cnt);
+                if (cur >= 0 && lane == 0) mz_add64(T + cur, cnt);
                 cur = c0;
                 cnt = 64;
             }
         } else {
-            if (cur >= 0 && lane == 0) lb_add64(T + cur, cnt);
+            if (cur >= 0 && lane == 0) mz_add64(T + cur, cnt);
             cur = -1;
             cnt = 0;
             if (head && cell >= 0) {
                 const unsigned long long rest = (hm >> lane) >> 1;
-                lb_add64(T + cell, (unsigned long long)(rest ? __builtin_ctzll(rest) + 1 : 64 - lane));
+                mz_add64(T + cell, (unsigned long long)(rest ? __builtin_ctzll(rest) + 1 : 64 - lane));
             }
         }
     }
-    if (cur >= 0 && lane == 0) lb_add64(T + cur, cnt);
+    if (cur >= 0 && lane == 0) mz_add64(T + cur, cnt);
     if (bad) status[0] = 1;                              // (every writer stores the same value)
 }
 
@@ -314,7 +306,7 @@ extern "C" int ullsam_rle_paint_labels(const int* counts, const long* offsets, c
     LB_FRAME_CHECK("rle_paint_labels");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const long per = (long)H * W;
-    if (hipMemsetAsync(raw, 0, (size_t)per * 4, s) != hipSuccess) { ullsam_set_error("rle_paint_labels: memset failed"); return -2; }
+    if (!mz_zero(raw, (size_t)per * 4, s)) { ullsam_set_error("rle_paint_labels: memset failed"); return -2; }
     if (N == 0) return 0;
     rle_paint_kernel<<<(unsigned)N, 256, 0, s>>>(counts, offsets, rank, N, per, raw, status);
     ULLSAM_LAUNCH_CHECK();
@@ -364,7 +356,7 @@ extern "C" int ullsam_label_overlap(const int* a, const int* b, int H, int W, in
     const long cells = ((long)na + 1) * ((long)nb + 1);
     ULLSAM_CHECK(cells <= (1L << 26), "label_overlap: (na + 1) * (nb + 1) must not exceed 2^26 cells (512 MiB of int64)");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(T, 0, (size_t)cells * 8, s) != hipSuccess || hipMemsetAsync(status, 0, 4, s) != hipSuccess) {
+    if (!mz_zero(T, (size_t)cells * 8, s) || !mz_zero(status, 4, s)) {
         ullsam_set_error("label_overlap: memset failed");
         return -2;
     }

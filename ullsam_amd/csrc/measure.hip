@@ -51,12 +51,6 @@ template <int C> struct MsRun {
     int mn[C ? C : 1], mx[C ? C : 1];
 };
 
-__device__ __forceinline__ void ms_add64(long* p, ms_u64 v) {
-    (void)__hip_atomic_fetch_add(reinterpret_cast<ms_u64*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void ms_send_min(int* p, int v) { if (mz_load(p) > v) (void)mz_min(p, v); }
-__device__ __forceinline__ void ms_send_max(int* p, int v) { if (mz_load(p) < v) mz_max(p, v); }
-
 // the address of the q-th 64-bit sum of table row `row`
 template <int C> __device__ __forceinline__ long* ms_sum_ptr(const MsOut& o, long row, int q) {
     if (q == 0) return o.area + row;
@@ -90,20 +84,8 @@ template <int C> __device__ __forceinline__ void ms_emit(const MsRun<C>& r, int 
         m[4 + c] = r.mn[c];
         m[4 + C + c] = r.mx[c];
     }
-    int slot = -1;
-    if (slots) {
-        unsigned h = ((unsigned)r.label * 0x9E3779B1u) >> 16;
-        for (int p = 0; p < MS_PROBES && slot < 0; ++p, ++h) {
-            int* kp = skey + (h & (unsigned)(slots - 1));
-            int k = __hip_atomic_load(kp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (k == 0) {
-                k = atomicCAS(kp, 0, r.label);
-                if (k == 0) k = r.label;
-            }
-            if (k == r.label) slot = (int)(h & (unsigned)(slots - 1));
-        }
-    }
-    if (slot >= 0) {
+    const int slot = mz_lds_slot<MS_PROBES>(r.label, slots, skey);
+    if (slot >= 0) {                                     // (this tail and m3_emit's are alike, but one template for both changes both tile kernels' code)
 #pragma unroll
         for (int i = 0; i < NQ; ++i)
             if (q[i]) atomicAdd(ssum + slot * NQ + i, q[i]);
@@ -116,19 +98,14 @@ template <int C> __device__ __forceinline__ void ms_emit(const MsRun<C>& r, int 
         const long row = (long)r.label - 1;
 #pragma unroll
         for (int i = 0; i < NQ; ++i)
-            if (q[i]) ms_add64(ms_sum_ptr<C>(out, row, i), q[i]);
+            if (q[i]) mz_add64(ms_sum_ptr<C>(out, row, i), q[i]);
 #pragma unroll
         for (int j = 0; j < NM; ++j) {
-            if (ms_ext_is_min<C>(j)) ms_send_min(ms_ext_ptr<C>(out, row, j), m[j]);
-            else ms_send_max(ms_ext_ptr<C>(out, row, j), m[j]);
+            if (ms_ext_is_min<C>(j)) mz_send_min(ms_ext_ptr<C>(out, row, j), m[j]);
+            else mz_send_max(ms_ext_ptr<C>(out, row, j), m[j]);
         }
     }
 }
-
-__device__ __forceinline__ int ms_pixel(const void* __restrict__ img, int bytes, long i) {
-    return bytes == 1 ? (int)reinterpret_cast<const unsigned char*>(img)[i] : (int)reinterpret_cast<const unsigned short*>(img)[i];
-}
-__device__ __forceinline__ int ms_clean(int v, int K) { return (v < 0 || v > K) ? 0 : v; }
 
 // grid (ceil(W / 256), ceil(H / 32)), block 256
 template <int C>
@@ -160,12 +137,12 @@ __global__ __launch_bounds__(256) void measure_kernel(const int* __restrict__ la
             if (x < W) {
                 l = labels[row + x];
                 if (l < 0 || l > K) { bad = true; l = 0; }
-                if (y > 0) up = ms_clean(labels[row - W + x], K);
-                if (y + 1 < H) dn = ms_clean(labels[row + W + x], K);
+                if (y > 0) up = mz_clean(labels[row - W + x], K);
+                if (y + 1 < H) dn = mz_clean(labels[row + W + x], K);
             }
             int lf = __shfl_up(l, 1, 64), rt = __shfl_down(l, 1, 64);
-            if (lane == 0) lf = xs > 0 ? ms_clean(labels[row + xs - 1], K) : -1;
-            if (lane == 63) rt = xs + 64 < W ? ms_clean(labels[row + xs + 64], K) : -1;
+            if (lane == 0) lf = xs > 0 ? mz_clean(labels[row + xs - 1], K) : -1;
+            if (lane == 63) rt = xs + 64 < W ? mz_clean(labels[row + xs + 64], K) : -1;
             const int k = l > 0 ? l : 0;
             int e = 0, ce = 0;
             int s[CC], mn[CC], mx[CC];
@@ -177,7 +154,7 @@ __global__ __launch_bounds__(256) void measure_kernel(const int* __restrict__ la
                 ce = (up != k && up > 0) + (dn != k && dn > 0) + (lf != k && lf > 0) + (rt != k && rt > 0);
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
-                    const int v = ms_pixel(img, bytes, (row + x) * C + c);
+                    const int v = mz_sample(img, bytes, (row + x) * C + c);
                     s[c] = v; s2[c] = (ms_u64)((unsigned)v * (unsigned)v); mn[c] = v; mx[c] = v;
                 }
             }
@@ -239,13 +216,13 @@ __global__ __launch_bounds__(256) void measure_kernel(const int* __restrict__ la
     for (int i = tid; i < slots * NQ; i += 256) {        // one global atomic per nonzero quantity and label
         const int key = skey[i / NQ];
         const ms_u64 v = ssum[i];
-        if (key > 0 && key <= K && v) ms_add64(ms_sum_ptr<C>(out, (long)key - 1, i % NQ), v);
+        if (key > 0 && key <= K && v) mz_add64(ms_sum_ptr<C>(out, (long)key - 1, i % NQ), v);
     }
     for (int i = tid; i < slots * NM; i += 256) {
         const int key = skey[i / NM], j = i % NM, v = sext[i];
         if (key <= 0 || key > K) continue;
-        if (ms_ext_is_min<C>(j)) { if (v != INT_MAX) ms_send_min(ms_ext_ptr<C>(out, (long)key - 1, j), v); }
-        else if (v >= 0) ms_send_max(ms_ext_ptr<C>(out, (long)key - 1, j), v);
+        if (ms_ext_is_min<C>(j)) { if (v != INT_MAX) mz_send_min(ms_ext_ptr<C>(out, (long)key - 1, j), v); }
+        else if (v >= 0) mz_send_max(ms_ext_ptr<C>(out, (long)key - 1, j), v);
     }
 }
 
@@ -264,10 +241,6 @@ __global__ __launch_bounds__(256) void measure_init_kernel(int K, int C, MsOut o
 }
 
 // ---- contacts -------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ mz_u64 ms_pair(int a, int b) {
-    if (a <= 0 || b <= 0 || a == b) return 0;
-    return a < b ? ((mz_u64)a << 32) | (mz_u64)b : ((mz_u64)b << 32) | (mz_u64)a;
-}
 // grid ceil(H / 4), block 256: one wave per row
 __global__ __launch_bounds__(256) void contacts_kernel(const int* __restrict__ labels, int H, int W, int K, mz_u64* __restrict__ keys,
                                                        long* __restrict__ counts, mz_u64 mask, int max_pairs, int* __restrict__ flags) {
@@ -284,12 +257,12 @@ __global__ __launch_bounds__(256) void contacts_kernel(const int* __restrict__ l
         if (x < W) {
             l = labels[row + x];
             if (l < 0 || l > K) { bad = true; l = 0; }
-            if (y + 1 < H) dn = ms_clean(labels[row + W + x], K);
+            if (y + 1 < H) dn = mz_clean(labels[row + W + x], K);
         }
         int rt = __shfl_down(l, 1, 64);
-        if (lane == 63) rt = xs + 64 < W ? ms_clean(labels[row + xs + 64], K) : 0;
-        mz_segment(rr, ms_pair(l, rt), xs, lane, add);
-        mz_segment(rd, ms_pair(l, dn), xs, lane, add);
+        if (lane == 63) rt = xs + 64 < W ? mz_clean(labels[row + xs + 64], K) : 0;
+        mz_segment(rr, mz_pair_key(l, rt), xs, lane, add);
+        mz_segment(rd, mz_pair_key(l, dn), xs, lane, add);
     }
     mz_flush(rr, lane, add);
     mz_flush(rd, lane, add);
@@ -352,11 +325,11 @@ extern "C" int ullsam_label_contacts(const int* labels, int H, int W, int K, uns
     ULLSAM_CHECK(cap >= 2 && (cap & (cap - 1)) == 0 && max_pairs >= 1 && 2L * max_pairs <= cap && cap <= (1L << 31),
                  "label_contacts: the capacity must be a power of two with 2 * max_pairs <= capacity <= 2^31");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    contacts_init_kernel<<<(unsigned)((cap + 255) / 256), 256, 0, s>>>(cap, keys, counts, flags);
+    contacts_init_kernel<<<mz_blocks(cap), 256, 0, s>>>(cap, keys, counts, flags);
     ULLSAM_LAUNCH_CHECK();
     contacts_kernel<<<(unsigned)((H + 3) / 4), 256, 0, s>>>(labels, H, W, K, keys, counts, (mz_u64)(cap - 1), max_pairs, flags);
     ULLSAM_LAUNCH_CHECK();
-    contacts_compact_kernel<<<(unsigned)((cap + 255) / 256), 256, 0, s>>>(keys, counts, cap, max_pairs, rows, flags);
+    contacts_compact_kernel<<<mz_blocks(cap), 256, 0, s>>>(keys, counts, cap, max_pairs, rows, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }

@@ -58,12 +58,6 @@ template <int C> struct M3Run {
     int mn[C ? C : 1], mx[C ? C : 1];
 };
 
-__device__ __forceinline__ void m3_add64(long* p, m3_u64 v) {
-    (void)__hip_atomic_fetch_add(reinterpret_cast<m3_u64*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void m3_send_min(int* p, int v) { if (mz_load(p) > v) (void)mz_min(p, v); }
-__device__ __forceinline__ void m3_send_max(int* p, int v) { if (mz_load(p) < v) mz_max(p, v); }
-
 // The tile kernel keeps the eight table pointers in the first 64 bytes of its LDS, in M3Out's order, and reads one where a total leaves for global
 // memory: held in scalar registers through the row loop they would push the kernel past its scalar registers (spills).
 // the address of the q-th 64-bit sum of table row `row`
@@ -101,19 +95,7 @@ template <int C> __device__ __forceinline__ void m3_emit(const M3Run<C>& r, int 
         m[6 + c] = r.mn[c];
         m[6 + C + c] = r.mx[c];
     }
-    int slot = -1;
-    if (slots) {
-        unsigned h = ((unsigned)r.label * 0x9E3779B1u) >> 16;
-        for (int p = 0; p < M3_PROBES && slot < 0; ++p, ++h) {
-            int* kp = skey + (h & (unsigned)(slots - 1));
-            int k = __hip_atomic_load(kp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (k == 0) {
-                k = atomicCAS(kp, 0, r.label);
-                if (k == 0) k = r.label;
-            }
-            if (k == r.label) slot = (int)(h & (unsigned)(slots - 1));
-        }
-    }
+    const int slot = mz_lds_slot<M3_PROBES>(r.label, slots, skey);
     if (slot >= 0) {
 #pragma unroll
         for (int i = 0; i < NQ; ++i)
@@ -127,19 +109,14 @@ template <int C> __device__ __forceinline__ void m3_emit(const M3Run<C>& r, int 
         const long row = (long)r.label - 1;
 #pragma unroll
         for (int i = 0; i < NQ; ++i)
-            if (q[i]) m3_add64(m3_sum_ptr<C>(out, row, i), q[i]);
+            if (q[i]) mz_add64(m3_sum_ptr<C>(out, row, i), q[i]);
 #pragma unroll
         for (int j = 0; j < NM; ++j) {
-            if (m3_ext_is_min<C>(j)) m3_send_min(m3_ext_ptr<C>(out, row, j), m[j]);
-            else m3_send_max(m3_ext_ptr<C>(out, row, j), m[j]);
+            if (m3_ext_is_min<C>(j)) mz_send_min(m3_ext_ptr<C>(out, row, j), m[j]);
+            else mz_send_max(m3_ext_ptr<C>(out, row, j), m[j]);
         }
     }
 }
-
-__device__ __forceinline__ int m3_sample(const void* __restrict__ img, int bytes, long i) {
-    return bytes == 1 ? (int)reinterpret_cast<const unsigned char*>(img)[i] : (int)reinterpret_cast<const unsigned short*>(img)[i];
-}
-__device__ __forceinline__ int m3_clean(int v, int K) { return (v < 0 || v > K) ? 0 : v; }
 
 // grid (ceil(W / 256), ceil(H / M3_TILE_R), ceil(Z / M3_TILE_P)), block 256
 template <int C>
@@ -177,14 +154,14 @@ __global__ __launch_bounds__(256) void measure3d_kernel(const int* __restrict__ 
             if (x < W) {
                 l = vol[row + x];
                 if (l < 0 || l > K) { bad = true; l = 0; }
-                if (y > 0) up = m3_clean(vol[row - W + x], K);
-                if (y + 1 < H) dn = m3_clean(vol[row + W + x], K);
-                if (z > 0) zb = m3_clean(vol[row - plane + x], K);
-                if (z + 1 < Z) zf = m3_clean(vol[row + plane + x], K);
+                if (y > 0) up = mz_clean(vol[row - W + x], K);
+                if (y + 1 < H) dn = mz_clean(vol[row + W + x], K);
+                if (z > 0) zb = mz_clean(vol[row - plane + x], K);
+                if (z + 1 < Z) zf = mz_clean(vol[row + plane + x], K);
             }
             int lf = __shfl_up(l, 1, 64), rt = __shfl_down(l, 1, 64);
-            if (lane == 0) lf = xs > 0 ? m3_clean(vol[row + xs - 1], K) : -1;
-            if (lane == 63) rt = xs + 64 < W ? m3_clean(vol[row + xs + 64], K) : -1;
+            if (lane == 0) lf = xs > 0 ? mz_clean(vol[row + xs - 1], K) : -1;
+            if (lane == 63) rt = xs + 64 < W ? mz_clean(vol[row + xs + 64], K) : -1;
             const int k = l > 0 ? l : 0;
             m3_u64 pk = 0;                               // boundary | fz << 8 | fy << 16 | fx << 24 | cz << 32 | cy << 40 | cx << 48
             int s[CC], mn[CC], mx[CC];
@@ -199,7 +176,7 @@ __global__ __launch_bounds__(256) void measure3d_kernel(const int* __restrict__ 
                      ((m3_u64)cy << 40) | ((m3_u64)cx << 48);
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
-                    const int v = m3_sample(img, bytes, (row + x) * C + c);
+                    const int v = mz_sample(img, bytes, (row + x) * C + c);
                     s[c] = v; s2[c] = (m3_u64)((unsigned)v * (unsigned)v); mn[c] = v; mx[c] = v;
                 }
             }
@@ -266,13 +243,13 @@ __global__ __launch_bounds__(256) void measure3d_kernel(const int* __restrict__ 
     for (int i = tid; i < slots * NQ; i += 256) {        // one global atomic per nonzero quantity and label
         const int key = skey[i / NQ];
         const m3_u64 v = ssum[i];
-        if (key > 0 && key <= K && v) m3_add64(m3_sum_ptr<C>(out, (long)key - 1, i % NQ), v);
+        if (key > 0 && key <= K && v) mz_add64(m3_sum_ptr<C>(out, (long)key - 1, i % NQ), v);
     }
     for (int i = tid; i < slots * NM; i += 256) {
         const int key = skey[i / NM], j = i % NM, v = sext[i];
         if (key <= 0 || key > K) continue;
-        if (m3_ext_is_min<C>(j)) { if (v != INT_MAX) m3_send_min(m3_ext_ptr<C>(out, (long)key - 1, j), v); }
-        else if (v >= 0) m3_send_max(m3_ext_ptr<C>(out, (long)key - 1, j), v);
+        if (m3_ext_is_min<C>(j)) { if (v != INT_MAX) mz_send_min(m3_ext_ptr<C>(out, (long)key - 1, j), v); }
+        else if (v >= 0) mz_send_max(m3_ext_ptr<C>(out, (long)key - 1, j), v);
     }
 }
 
@@ -291,10 +268,6 @@ __global__ __launch_bounds__(256) void measure3d_init_kernel(int K, int C, M3Out
 }
 
 // ---- contacts -------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ mz_u64 m3_pair(int a, int b) {
-    if (a <= 0 || b <= 0 || a == b) return 0;
-    return a < b ? ((mz_u64)a << 32) | (mz_u64)b : ((mz_u64)b << 32) | (mz_u64)a;
-}
 // grid ceil(Z * H / 4), block 256: one wave per (z, y) row
 __global__ __launch_bounds__(256) void contacts3d_kernel(const int* __restrict__ vol, int Z, int H, int W, int K, mz_u64* __restrict__ keys,
                                                          long* __restrict__ counts, mz_u64 mask, int max_pairs, int* __restrict__ flags) {
@@ -314,14 +287,14 @@ __global__ __launch_bounds__(256) void contacts3d_kernel(const int* __restrict__
         if (x < W) {
             l = vol[row + x];
             if (l < 0 || l > K) { bad = true; l = 0; }
-            if (y + 1 < H) dn = m3_clean(vol[row + W + x], K);
-            if (z + 1 < Z) zf = m3_clean(vol[row + plane + x], K);
+            if (y + 1 < H) dn = mz_clean(vol[row + W + x], K);
+            if (z + 1 < Z) zf = mz_clean(vol[row + plane + x], K);
         }
         int rt = __shfl_down(l, 1, 64);
-        if (lane == 63) rt = xs + 64 < W ? m3_clean(vol[row + xs + 64], K) : 0;
-        mz_segment(rx, m3_pair(l, rt), xs, lane, addx);
-        mz_segment(ry, m3_pair(l, dn), xs, lane, addy);
-        mz_segment(rz, m3_pair(l, zf), xs, lane, addz);
+        if (lane == 63) rt = xs + 64 < W ? mz_clean(vol[row + xs + 64], K) : 0;
+        mz_segment(rx, mz_pair_key(l, rt), xs, lane, addx);
+        mz_segment(ry, mz_pair_key(l, dn), xs, lane, addy);
+        mz_segment(rz, mz_pair_key(l, zf), xs, lane, addz);
     }
     mz_flush(rx, lane, addx);
     mz_flush(ry, lane, addy);
@@ -388,11 +361,11 @@ extern "C" int ullsam_object_contacts3d(const int* volume, int Z, int H, int W, 
     ULLSAM_CHECK(cap >= 2 && (cap & (cap - 1)) == 0 && max_pairs >= 1 && 2L * max_pairs <= cap && cap <= (1L << 31),
                  "object_contacts3d: the capacity must be a power of two with 2 * max_pairs <= capacity <= 2^31");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    contacts3d_init_kernel<<<(unsigned)((cap + 255) / 256), 256, 0, s>>>(cap, keys, counts, flags);
+    contacts3d_init_kernel<<<mz_blocks(cap), 256, 0, s>>>(cap, keys, counts, flags);
     ULLSAM_LAUNCH_CHECK();
     contacts3d_kernel<<<(unsigned)(((long)Z * H + 3) / 4), 256, 0, s>>>(volume, Z, H, W, K, keys, counts, (mz_u64)(cap - 1), max_pairs, flags);
     ULLSAM_LAUNCH_CHECK();
-    contacts3d_compact_kernel<<<(unsigned)((cap + 255) / 256), 256, 0, s>>>(keys, counts, cap, max_pairs, rows, flags);
+    contacts3d_compact_kernel<<<mz_blocks(cap), 256, 0, s>>>(keys, counts, cap, max_pairs, rows, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }

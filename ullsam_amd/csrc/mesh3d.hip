@@ -23,7 +23,7 @@
 // cell that come before it in raster order has its id, and adds +1 per corner and face, -1 per edge and -1 for itself: summed over the object that
 // is V - E + F - C.  A pinch edge (k, not k, k, not k around it) is counted by the first of its two voxels of k.  A voxel whose 26 neighbours all
 // have its id sums to 0 and sends nothing.
-#include "pair_table.h"
+#include "label_common.h"
 
 #define MS_TILE_X 64
 #define MS_TILE_Y 4      // rows of a tile (ops.MESH3D_TILE_Y)
@@ -52,15 +52,6 @@ __device__ __forceinline__ ms_u64 ms_corner_key(ms_u64 fkey, int j, int H, int W
     const unsigned c = (ms_quad[d] >> (3 * j)) & 7u;
     const ms_u64 cx = x + (c & 1u), cy = y + ((c >> 1) & 1u), cz = z + ((c >> 2) & 1u);
     return (fkey & ~MS_ID_MASK) | ((cz * (ms_u64)(H + 1) + cy) * (ms_u64)(W + 1) + cx);
-}
-
-__device__ __forceinline__ int ms_wave_scan(int v, int lane) {   // inclusive
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
 }
 
 // ---- faces --------------------------------------------------------------------------------------------------------------------------------------
@@ -145,7 +136,7 @@ __global__ __launch_bounds__(256) void mesh3d_faces_kernel(const int* __restrict
         m[dz] = (x < W && y < H && z0 + dz < Z) ? (int)masks[(z0 + dz) * plane + (long)y * W + x] : 0;
         n += __popc((unsigned)m[dz]);
     }
-    const int inc = ms_wave_scan(n, tx);
+    const int inc = wave_scan_incl(n, tx);
     if (tx == 63) wsum[ty] = inc;
     __syncthreads();
     int before = 0;
@@ -202,7 +193,7 @@ __global__ __launch_bounds__(256) void mesh3d_heads_kernel(const ms_u64* __restr
         __syncthreads();
         if (tid == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
     } else {
-        const int inc = ms_wave_scan(cnt, lane);
+        const int inc = wave_scan_incl(cnt, lane);
         if (lane == 63) wsum[wave] = inc;
         __syncthreads();
         int before = 0;
@@ -324,8 +315,8 @@ __global__ __launch_bounds__(256) void mesh3d_topology_kernel(const int* __restr
         const int q = ms_pinch<ms_bit(0, 1, 1), ms_bit(0, 1, 0), ms_bit(0, 0, 1)>(same) + ms_pinch<ms_bit(0, 1, -1), ms_bit(0, 1, 0), ms_bit(0, 0, -1)>(same) +
                       ms_pinch<ms_bit(1, 0, 1), ms_bit(1, 0, 0), ms_bit(0, 0, 1)>(same) + ms_pinch<ms_bit(1, 0, -1), ms_bit(1, 0, 0), ms_bit(0, 0, -1)>(same) +
                       ms_pinch<ms_bit(1, 1, 0), ms_bit(1, 0, 0), ms_bit(0, 1, 0)>(same) + ms_pinch<ms_bit(1, -1, 0), ms_bit(1, 0, 0), ms_bit(0, -1, 0)>(same);
-        if (e) (void)__hip_atomic_fetch_add(reinterpret_cast<ms_u64*>(euler + (l - 1)), (ms_u64)(long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (q) (void)__hip_atomic_fetch_add(reinterpret_cast<ms_u64*>(pinch + (l - 1)), (ms_u64)q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (e) mz_add64(euler + (l - 1), (ms_u64)(long)e);
+        if (q) mz_add64(pinch + (l - 1), (ms_u64)q);
     }
     if (bad) mz_store(flags + 0, 1);
 }
@@ -363,7 +354,7 @@ extern "C" int ullsam_mesh3d_faces(const int* volume, const unsigned char* masks
 extern "C" int ullsam_mesh3d_corners(const unsigned long long* fkeys, long F, int H, int W, unsigned long long* ckeys, void* stream) {
     ULLSAM_CHECK(F >= 0 && F <= 2147483647L && H >= 1 && W >= 1 && H <= MS_MAX_SIDE && W <= MS_MAX_SIDE, "mesh3d_corners: need 0 <= F <= 2^31 - 1 and 1 <= H, W <= 32767");
     if (F == 0) return 0;
-    mesh3d_corners_kernel<<<(unsigned)((F + 255) / 256), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(fkeys, F, H, W, ckeys);
+    mesh3d_corners_kernel<<<mz_blocks(F), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(fkeys, F, H, W, ckeys);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -396,7 +387,7 @@ extern "C" int ullsam_mesh3d_quads(const unsigned long long* fkeys, long F, cons
     ULLSAM_CHECK(F >= 0 && F <= 2147483647L && V >= 0 && V <= 2147483647L && H >= 1 && W >= 1 && H <= MS_MAX_SIDE && W <= MS_MAX_SIDE,
                  "mesh3d_quads: need 0 <= F, V <= 2^31 - 1 and 1 <= H, W <= 32767");
     if (F == 0) return 0;
-    mesh3d_quads_kernel<<<(unsigned)((4 * F + 255) / 256), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(fkeys, F, ukeys, V, H, W, quads);
+    mesh3d_quads_kernel<<<mz_blocks(4 * F), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(fkeys, F, ukeys, V, H, W, quads);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }

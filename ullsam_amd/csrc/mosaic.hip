@@ -14,7 +14,7 @@
 //     >= 2 * max_pairs.  The number of claimed slots is counted; once it exceeds max_pairs further NEW keys are refused and flags[1] is set,
 //     so the table never fills and a probe sequence always ends.
 // Merge.  One thread per slot: n * den >= num * (A_s + A_t - n) in 64-bit (all three are at most |R| < 2^31, num <= den < 2^31), then the
-// union of the two ids in parent[G + 1] by linking the LARGER root under the smaller one with an atomicMin (rg_union_glb's loop, regions.hip),
+// union of the two ids in parent[G + 1] by linking the LARGER root under the smaller one with an atomicMin (mz_union, label_common.h),
 // so a component's root is its smallest id whatever the order.  A flatten pass leaves parent[g] = that root.
 // Stats.  One wave per row of a tile's core: visible area and inclusive XYXY box per representative, one atomicAdd per run, box bounds sent
 // only when a relaxed load says they would improve (bounds move one way: a stale load costs an atomic, never a result).
@@ -25,7 +25,7 @@
 // in 64 bits.
 // Every descriptor (seam regions, cores) is clipped against the tiles and the frame in the kernels, and an id outside 0..K_t reads as
 // background and sets flags[0]: malformed input cannot read or write outside the buffers.
-#include "pair_table.h"   // the relaxed atomics, the runs of equal keys along a row and the pair table (shared with measure.hip)
+#include "pair_table.h"   // the runs of equal keys along a row and the pair table; through it label_common.h: the relaxed atomics, the union-find
 #include <limits.h>
 
 // ---- seam counting --------------------------------------------------------------------------------------------------------------------
@@ -80,25 +80,6 @@ __global__ __launch_bounds__(256) void mosaic_seams_kernel(const int* __restrict
 }
 
 // ---- merge + union-find -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int mz_find(const int* L, int i) {
-    int q = mz_load(L + i);
-    while (q != i) { i = q; q = mz_load(L + i); }
-    return i;
-}
-__device__ __forceinline__ void mz_union(int* L, int a, int b) {
-    const int a0 = a, b0 = b;
-    for (;;) {
-        a = mz_find(L, a);
-        b = mz_find(L, b);
-        if (a == b) break;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = mz_min(L + a, b);                // a was a root when read: link it under the smaller root
-        if (old == a) { a = b; break; }
-        a = old;                                         // somebody linked a first: a ~ old still has to meet b
-    }
-    if (a < a0) mz_min(L + a0, a);                       // shorten the two chains: `a` is an ancestor of both, and a parent only moves down
-    if (a < b0) mz_min(L + b0, a);
-}
 __global__ __launch_bounds__(256) void mosaic_iota_kernel(long n, int* __restrict__ parent) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) parent[i] = (int)i;
@@ -168,10 +149,10 @@ __global__ __launch_bounds__(256) void mosaic_stats_kernel(const int* __restrict
         mz_add(areas + v, n);
         const int xa = c.left + x0, xb = xa + n - 1;
         int* bx = boxes + 4 * v;
-        if (mz_load(bx + 0) > xa) mz_min(bx + 0, xa);
-        if (mz_load(bx + 1) > y) mz_min(bx + 1, y);
-        if (mz_load(bx + 2) < xb) mz_max(bx + 2, xb);
-        if (mz_load(bx + 3) < y) mz_max(bx + 3, y);
+        mz_send_min(bx + 0, xa);
+        mz_send_min(bx + 1, y);
+        mz_send_max(bx + 2, xb);
+        mz_send_max(bx + 3, y);
     };
     MzRun run = {0, 0, 0};
     bool bad = false;
@@ -244,8 +225,6 @@ __global__ __launch_bounds__(256) void mosaic_compact_kernel(const int* __restri
     }
 }
 
-__device__ __forceinline__ int mz_look(int l, int b0, int kt, const int* __restrict__ log) { return (l > 0 && l <= kt) ? log[b0 + l] : 0; }
-
 // grid (ceil(max core rows / 4), T), block 256: one wave per row of a core.  vec: both buffers start on a 16-byte boundary.
 __global__ __launch_bounds__(256) void mosaic_paste_kernel(const int* __restrict__ tiles, int th, int tw, const int* __restrict__ base, long G,
                                                            const int* __restrict__ cores, const int* __restrict__ log, int H, int W, int vec,
@@ -283,8 +262,6 @@ __global__ __launch_bounds__(256) void mosaic_paste_kernel(const int* __restrict
 #define MZ_TILES_CHECK(what)                                                                                                     \
     ULLSAM_CHECK(T >= 1 && T <= 65535 && th > 0 && tw > 0 && G >= 0 && G <= 2147483646L, what ": need 1 <= T <= 65535, th, tw > 0, 0 <= G <= 2^31 - 2")
 
-static bool mz_zero(void* p, size_t bytes, hipStream_t s) { return bytes == 0 || hipMemsetAsync(p, 0, bytes, s) == hipSuccess; }
-
 extern "C" int ullsam_mosaic_seams(const int* tiles, int T, int th, int tw, const int* base, long G, const int* seams, int S, int max_rows,
                                    unsigned long long* keys, int* counts, long cap, int max_pairs, int* areas, int* flags, void* stream) {
     MZ_TILES_CHECK("mosaic_seams");
@@ -308,12 +285,12 @@ extern "C" int ullsam_mosaic_union(const unsigned long long* keys, const int* co
     ULLSAM_CHECK(G >= 0 && G <= 2147483646L && cap >= 0 && cap <= (1L << 31), "mosaic_union: need 0 <= G <= 2^31 - 2 and 0 <= slots <= 2^31");
     ULLSAM_CHECK(num > 0 && num <= den && den < (1L << 31), "mosaic_union: need 0 < num <= den < 2^31");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    mosaic_iota_kernel<<<(unsigned)((G + 1 + 255) / 256), 256, 0, s>>>(G + 1, parent);
+    mosaic_iota_kernel<<<mz_blocks(G + 1), 256, 0, s>>>(G + 1, parent);
     ULLSAM_LAUNCH_CHECK();
     if (cap > 0 && G > 0) {
-        mosaic_merge_kernel<<<(unsigned)((cap + 255) / 256), 256, 0, s>>>(keys, counts, cap, areas, G, num, den, parent, flags);
+        mosaic_merge_kernel<<<mz_blocks(cap), 256, 0, s>>>(keys, counts, cap, areas, G, num, den, parent, flags);
         ULLSAM_LAUNCH_CHECK();
-        mosaic_flatten_kernel<<<(unsigned)((G + 1 + 255) / 256), 256, 0, s>>>(G + 1, parent);
+        mosaic_flatten_kernel<<<mz_blocks(G + 1), 256, 0, s>>>(G + 1, parent);
         ULLSAM_LAUNCH_CHECK();
     }
     return 0;
@@ -324,7 +301,7 @@ extern "C" int ullsam_mosaic_stats(const int* tiles, int T, int th, int tw, cons
     MZ_TILES_CHECK("mosaic_stats");
     ULLSAM_CHECK(H > 0 && W > 0 && max_rows >= 0 && max_rows <= th, "mosaic_stats: need H, W > 0 and 0 <= max_rows <= th");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    mosaic_stats_init_kernel<<<(unsigned)((G + 1 + 255) / 256), 256, 0, s>>>(G + 1, areas_raw, boxes_raw);
+    mosaic_stats_init_kernel<<<mz_blocks(G + 1), 256, 0, s>>>(G + 1, areas_raw, boxes_raw);
     ULLSAM_LAUNCH_CHECK();
     if (max_rows == 0) return 0;
     mosaic_stats_kernel<<<dim3((unsigned)((max_rows + 3) / 4), (unsigned)T), 256, 0, s>>>(tiles, th, tw, base, G, cores, parent, H, W, areas_raw,

@@ -22,39 +22,15 @@
 //               repeats from that loop's leader until it stands on an outer loop.
 // flags i32 [8]: [0] = a label below 0 or above K (the pixel counts as background), or an index that left its table (skipped; nothing is indexed with
 // it), [1] = E, [2] = the corners, [3] = the leaders, [4] = the cursor of the list, [5] = a parent chain longer than L.
-#include "pair_table.h"
+#include "label_common.h"
 #include <stdint.h>
 
 #define OL_BLOCK 256
 #define OL_PER 8
 #define OL_CHUNK (OL_BLOCK * OL_PER)
 
-__device__ __forceinline__ bool ol_in(long i, long n) { return i >= 0 && i < n; }
-
 // ---- scan -----------------------------------------------------------------------------------------------------------------------------------
-// the exclusive scan of v over the workgroup's OL_BLOCK threads; total = the sum over all of them
-__device__ __forceinline__ int ol_block_exscan(int v, int& total) {
-    __shared__ int s_wave[OL_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    __syncthreads();                                      // (the table may still be read from an earlier call)
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int i = 0; i < OL_BLOCK / 64; ++i) {
-        const int t = s_wave[i];
-        if (i < wave) before += t;
-        all += t;
-    }
-    total = all;
-    return before + inc - v;
-}
+// (block_exscan<OL_BLOCK>: label_common.h)
 template <bool POP> __device__ __forceinline__ int ol_value(unsigned char b) { return POP ? __builtin_popcount((unsigned)b & 15u) : (b != 0); }
 
 // the OL_PER values of a thread, bounds checked; returns their sum
@@ -70,7 +46,7 @@ template <bool POP> __device__ __forceinline__ int ol_take(const unsigned char* 
 template <bool POP> __global__ __launch_bounds__(OL_BLOCK) void outline_sums_kernel(const unsigned char* __restrict__ vals, long n, int* __restrict__ sums) {
     int c[OL_PER], total;
     const int mine = ol_take<POP>(vals, n, (long)blockIdx.x * OL_CHUNK + (long)threadIdx.x * OL_PER, c);
-    (void)ol_block_exscan(mine, total);
+    (void)block_exscan<OL_BLOCK>(mine, total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 // one workgroup: sums[b] = the sum of the blocks before b; *total = the sum of all
@@ -80,7 +56,7 @@ __global__ __launch_bounds__(OL_BLOCK) void outline_scan_sums_kernel(int* __rest
         const long i = base + threadIdx.x;
         const int v = i < nb ? sums[i] : 0;
         int all;
-        const int ex = ol_block_exscan(v, all);
+        const int ex = block_exscan<OL_BLOCK>(v, all);
         if (i < nb) sums[i] = carry + ex;
         carry += all;
     }
@@ -92,7 +68,7 @@ __global__ __launch_bounds__(OL_BLOCK) void outline_offsets_kernel(const unsigne
     int c[OL_PER], total;
     const long i0 = (long)blockIdx.x * OL_CHUNK + (long)threadIdx.x * OL_PER;
     const int mine = ol_take<POP>(vals, n, i0, c);
-    int at = sums[blockIdx.x] + ol_block_exscan(mine, total);
+    int at = sums[blockIdx.x] + block_exscan<OL_BLOCK>(mine, total);
 #pragma unroll
     for (int j = 0; j < OL_PER; ++j) {
         if (i0 + j < n) off[i0 + j] = at;
@@ -142,7 +118,7 @@ __global__ __launch_bounds__(OL_BLOCK) void outline_successors_kernel(const int*
         const int ts = left ? (s + 3) & 3 : straight ? s : (s + 1) & 3;
         const unsigned tm = mask[tp] & 15u;
         const long t = (long)off[tp] + __builtin_popcount(tm & ((1u << ts) - 1u));
-        if (!ol_in(e, E) || !ol_in(t, E) || !(tm >> ts & 1u)) {            // (hand-made masks or offsets)
+        if (!mz_in(e, E) || !mz_in(t, E) || !(tm >> ts & 1u)) {            // (hand-made masks or offsets)
             mz_store(flags + 0, 1);
         } else {
             eid[e] = (int)(4 * p + s);
@@ -159,7 +135,7 @@ __global__ __launch_bounds__(OL_BLOCK) void outline_rank_init_kernel(const int* 
     const long e = (long)blockIdx.x * OL_BLOCK + threadIdx.x;
     if (e >= E) return;
     int j = succ[e];
-    if (!ol_in(j, E)) {                                   // (a hand-made map)
+    if (!mz_in(j, E)) {                                   // (a hand-made map)
         mz_store(flags + 0, 1);
         j = (int)e;
     }
@@ -185,7 +161,7 @@ __global__ __launch_bounds__(OL_BLOCK) void outline_rank_finish_kernel(const int
         int r = 0;
         if (me.y != 0) {
             const int j = succ[me.x];                     // the leader's successor is one step short of a whole turn
-            if (ol_in(j, E)) r = st[j].y + 1 - me.y;
+            if (mz_in(j, E)) r = st[j].y + 1 - me.y;
         }
         leader[e] = me.x;
         rank[e] = r;
@@ -208,7 +184,7 @@ __global__ __launch_bounds__(OL_BLOCK) void outline_collect_kernel(const int* __
     long p = 0;
     if (e < E && leader[e] == (int)e) {
         p = (long)(eid[e] >> 2);
-        is = ol_in(p, n);
+        is = mz_in(p, n);
         if (!is) mz_store(flags + 0, 1);
     }
     const mz_u64 m = __ballot(is);
@@ -223,14 +199,13 @@ __global__ __launch_bounds__(OL_BLOCK) void outline_collect_kernel(const int* __
     else mz_store(flags + 0, 1);
 }
 
-__device__ __forceinline__ void ol_add64(long long* p, long long v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // the loop of edge e, or -1 (a hand-made table)
 __device__ __forceinline__ int ol_loop(const int* __restrict__ leader, const int* __restrict__ loop_of, long E, long L, long e) {
     const int l = leader[e];
-    if (!ol_in(l, E)) return -1;
+    if (!mz_in(l, E)) return -1;
     const int lp = loop_of[l];
-    return ol_in(lp, L) ? lp : -1;
+    return mz_in(lp, L) ? lp : -1;
 }
 // OL_RUN consecutive edges a thread, summed while the loop stays the same; then the wave merges its lanes key by key: one atomic pair for every
 // distinct loop of the wave, however the edges arrive.  Sums of integers: the order of arrival does not matter.
@@ -249,7 +224,7 @@ __device__ __forceinline__ void ol_send(int lp, int cnt, long long sum, int* __r
         }
         if ((threadIdx.x & 63) == 0) {
             mz_add(edges + key, c);
-            ol_add64(area2 + key, v);
+            mz_add64(area2 + key, v);
         }
         todo &= ~__ballot(mine);
     }
@@ -295,7 +270,7 @@ __global__ __launch_bounds__(OL_BLOCK) void outline_order_kernel(const int* __re
     if (e >= E) return;
     const int lp = ol_loop(leader, loop_of, E, L, e);
     const long slot = lp < 0 ? -1 : (long)estart[lp] + rank[e];
-    if (!ol_in(slot, E)) {
+    if (!mz_in(slot, E)) {
         mz_store(flags + 0, 1);
         return;
     }
@@ -309,7 +284,7 @@ __global__ __launch_bounds__(OL_BLOCK) void outline_vertices_kernel(const int* _
     const long i = (long)blockIdx.x * OL_BLOCK + threadIdx.x;
     if (i >= E || !corner[i]) return;
     const long at = coff[i];
-    if (!ol_in(at, N)) return;
+    if (!mz_in(at, N)) return;
     const int id = reid[i], s = id & 3, p = id >> 2;
     vertices[2 * at + 0] = p % W + (s == 1 || s == 2);
     vertices[2 * at + 1] = p / W + (s == 2 || s == 3);
@@ -327,12 +302,12 @@ __global__ __launch_bounds__(OL_BLOCK) void outline_parents_kernel(const int* __
     long cur = i;
     for (long hops = 0; area2[cur] <= 0; ++hops) {
         const int le = lead[cur];
-        if (hops >= L || !ol_in(le, E)) {                 // (every hop moves strictly left: L hops mean a hand-made table)
+        if (hops >= L || !mz_in(le, E)) {                 // (every hop moves strictly left: L hops mean a hand-made table)
             mz_store(flags + 5, 1);
             break;
         }
         long p = (long)(eid[le] >> 2);
-        if (!ol_in(p, (long)H * W)) {
+        if (!mz_in(p, (long)H * W)) {
             mz_store(flags + 0, 1);
             break;
         }
@@ -343,7 +318,7 @@ __global__ __launch_bounds__(OL_BLOCK) void outline_parents_kernel(const int* __
             --p;
         }
         const long e = (long)off[p] + __builtin_popcount((unsigned)mask[p] & 7u);   // the left side of that pixel
-        const int nxt = ol_in(e, E) ? ol_loop(leader, loop_of, E, L, e) : -1;
+        const int nxt = mz_in(e, E) ? ol_loop(leader, loop_of, E, L, e) : -1;
         if (nxt < 0) {
             mz_store(flags + 0, 1);
             break;
@@ -358,7 +333,6 @@ __global__ __launch_bounds__(OL_BLOCK) void outline_parents_kernel(const int* __
 #define OL_FRAME_CHECK(what) ULLSAM_CHECK(H >= 1 && W >= 1 && (long)H * W < OL_MAX_PIXELS, what ": need 1 <= H, W and H * W < 2^29")
 #define OL_EDGES_CHECK(what) ULLSAM_CHECK(E >= 0 && E < 4 * OL_MAX_PIXELS, what ": need 0 <= E < 2^31")
 
-static unsigned ol_blocks(long n) { return (unsigned)((n + OL_BLOCK - 1) / OL_BLOCK); }
 static long ol_chunks(long n) { return (n + OL_CHUNK - 1) / OL_CHUNK; }
 
 template <bool POP> static int ol_scan(const unsigned char* vals, long n, int* off, int* sums, int* total, hipStream_t s) {
@@ -377,7 +351,7 @@ extern "C" int ullsam_outline_sides(const int* labels, int H, int W, long K, uns
     ULLSAM_CHECK(K >= 0 && K <= 2147483647L, "outline_sides: need 0 <= K <= 2^31 - 1");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const long n = (long)H * W;
-    outline_sides_kernel<<<ol_blocks(n), OL_BLOCK, 0, s>>>(labels, H, W, K, mask, flags);
+    outline_sides_kernel<<<mz_blocks(n, OL_BLOCK), OL_BLOCK, 0, s>>>(labels, H, W, K, mask, flags);
     ULLSAM_LAUNCH_CHECK();
     return ol_scan<true>(mask, n, off, sums, flags + 1, s);
 }
@@ -401,7 +375,7 @@ extern "C" int ullsam_outline_successors(const int* labels, int H, int W, const 
     OL_EDGES_CHECK("outline_successors");
     ULLSAM_CHECK(connectivity == 4 || connectivity == 8, "outline_successors: connectivity is 4 or 8");
     if (E == 0) return 0;
-    outline_successors_kernel<<<ol_blocks((long)H * W), OL_BLOCK, 0, reinterpret_cast<hipStream_t>(stream)>>>(labels, H, W, mask, off, E, connectivity, eid, succ,
+    outline_successors_kernel<<<mz_blocks((long)H * W, OL_BLOCK), OL_BLOCK, 0, reinterpret_cast<hipStream_t>(stream)>>>(labels, H, W, mask, off, E, connectivity, eid, succ,
                                                                                                            pdir, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
@@ -417,16 +391,16 @@ extern "C" int ullsam_outline_rank(const int* succ, const int* eid, const unsign
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     int4* a = reinterpret_cast<int4*>(ws);
     int4* b = a + E;
-    outline_rank_init_kernel<<<ol_blocks(E), OL_BLOCK, 0, s>>>(succ, E, a, flags);
+    outline_rank_init_kernel<<<mz_blocks(E, OL_BLOCK), OL_BLOCK, 0, s>>>(succ, E, a, flags);
     ULLSAM_LAUNCH_CHECK();
     for (int r = 0; r < rounds; ++r) {
-        outline_rank_round_kernel<<<ol_blocks(E), OL_BLOCK, 0, s>>>(E, 1 << r, a, b);
+        outline_rank_round_kernel<<<mz_blocks(E, OL_BLOCK), OL_BLOCK, 0, s>>>(E, 1 << r, a, b);
         ULLSAM_LAUNCH_CHECK();
         int4* t = a;
         a = b;
         b = t;
     }
-    outline_rank_finish_kernel<<<ol_blocks(E), OL_BLOCK, 0, s>>>(succ, eid, pdir, E, a, leader, rank, flags);
+    outline_rank_finish_kernel<<<mz_blocks(E, OL_BLOCK), OL_BLOCK, 0, s>>>(succ, eid, pdir, E, a, leader, rank, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -436,7 +410,7 @@ extern "C" int ullsam_outline_collect(const int* labels, long n, const int* eid,
     OL_EDGES_CHECK("outline_collect");
     ULLSAM_CHECK(n >= 1 && n < OL_MAX_PIXELS && room >= 0, "outline_collect: need 1 <= n < 2^29 and room >= 0");
     if (E == 0) return 0;
-    outline_collect_kernel<<<ol_blocks(E), OL_BLOCK, 0, reinterpret_cast<hipStream_t>(stream)>>>(labels, n, eid, leader, E, reinterpret_cast<mz_u64*>(list), room,
+    outline_collect_kernel<<<mz_blocks(E, OL_BLOCK), OL_BLOCK, 0, reinterpret_cast<hipStream_t>(stream)>>>(labels, n, eid, leader, E, reinterpret_cast<mz_u64*>(list), room,
                                                                                                 flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
@@ -452,7 +426,7 @@ extern "C" int ullsam_outline_loops(const int* eid, const int* leader, const int
         ullsam_set_error("outline_loops: memset failed");
         return -2;
     }
-    outline_loops_kernel<<<ol_blocks((E + OL_RUN - 1) / OL_RUN), OL_BLOCK, 0, s>>>(eid, leader, loop_of, E, L, W, edges, area2, flags);
+    outline_loops_kernel<<<mz_blocks((E + OL_RUN - 1) / OL_RUN, OL_BLOCK), OL_BLOCK, 0, s>>>(eid, leader, loop_of, E, L, W, edges, area2, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -467,7 +441,7 @@ extern "C" int ullsam_outline_order(const int* eid, const unsigned char* pdir, c
         ullsam_set_error("outline_order: memset failed");
         return -2;
     }
-    outline_order_kernel<<<ol_blocks(E), OL_BLOCK, 0, s>>>(eid, pdir, leader, rank, loop_of, estart, E, L, reid, corner, flags);
+    outline_order_kernel<<<mz_blocks(E, OL_BLOCK), OL_BLOCK, 0, s>>>(eid, pdir, leader, rank, loop_of, estart, E, L, reid, corner, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -476,7 +450,7 @@ extern "C" int ullsam_outline_vertices(const int* reid, const unsigned char* cor
     OL_EDGES_CHECK("outline_vertices");
     ULLSAM_CHECK(N >= 0 && N <= E && W >= 1, "outline_vertices: need 0 <= N <= E and W >= 1");
     if (E == 0 || N == 0) return 0;
-    outline_vertices_kernel<<<ol_blocks(E), OL_BLOCK, 0, reinterpret_cast<hipStream_t>(stream)>>>(reid, corner, coff, E, W, N, vertices);
+    outline_vertices_kernel<<<mz_blocks(E, OL_BLOCK), OL_BLOCK, 0, reinterpret_cast<hipStream_t>(stream)>>>(reid, corner, coff, E, W, N, vertices);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -487,7 +461,7 @@ extern "C" int ullsam_outline_parents(const int* labels, int H, int W, const uns
     OL_EDGES_CHECK("outline_parents");
     ULLSAM_CHECK(L >= 0 && L <= E, "outline_parents: need 0 <= L <= E");
     if (L == 0) return 0;
-    outline_parents_kernel<<<ol_blocks(L), OL_BLOCK, 0, reinterpret_cast<hipStream_t>(stream)>>>(labels, H, W, mask, off, eid, leader, loop_of, lead, area2, E, L,
+    outline_parents_kernel<<<mz_blocks(L, OL_BLOCK), OL_BLOCK, 0, reinterpret_cast<hipStream_t>(stream)>>>(labels, H, W, mask, off, eid, leader, loop_of, lead, area2, E, L,
                                                                                                 parent, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;

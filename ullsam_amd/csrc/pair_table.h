@@ -1,16 +1,8 @@
-// Shared by mosaic.hip (label pairs across tile seams) and measure.hip (label pairs across pixel sides): runs of equal keys along a row and the
-// open-addressing pair table in global memory.  Integer work only; what the table holds at the end does not depend on the order of arrival.
+// The row runs and the pair table of the label-image kernels, on top of label_common.h: runs of equal keys along a row (one atomic per run), and the
+// open-addressing table of id pairs in global memory (mosaic, stack, split*, measure*: seams, links, passes, contacts).  Integer work only; what
+// the table holds at the end does not depend on the order of arrival.
 #pragma once
-#include "common.h"
-
-typedef unsigned long long mz_u64;
-
-__device__ __forceinline__ int mz_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void mz_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void mz_add(int* p, int v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void mz_add(long* p, int v) { (void)__hip_atomic_fetch_add(p, (long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int mz_min(int* p, int v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void mz_max(int* p, int v) { (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+#include "label_common.h"
 
 // ---- runs of equal keys along a row ---------------------------------------------------------------------------------------------
 // Wave-uniform: a run of whole 64-pixel segments that has not been sent yet (key 0: none).
@@ -56,12 +48,13 @@ __device__ __forceinline__ mz_u64 mz_hash(mz_u64 k) {
     k ^= k >> 33;
     return k;
 }
-template <class CT>
-__device__ __forceinline__ void mz_pair_add(mz_u64 key, int n, mz_u64* __restrict__ keys, CT* __restrict__ counts, mz_u64 mask, int max_pairs,
-                                            int* __restrict__ flags) {
+// The probe loop: use(slot) is called with the slot of `key`, claimed if need be; flags[1] is set instead when the table refuses the key.  (A
+// form that returns the slot, or -1, changes the code of every kernel that counts pairs; this one compiles to what the three copies did.)
+template <class F>
+__device__ __forceinline__ void mz_pair_slot(mz_u64 key, mz_u64* __restrict__ keys, mz_u64 mask, int max_pairs, int* __restrict__ flags, F use) {
     mz_u64 slot = mz_hash(key) & mask;
     for (mz_u64 probes = 0; probes <= mask; ++probes, slot = (slot + 1) & mask) {
-        mz_u64 old = __hip_atomic_load(keys + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        mz_u64 old = mz_load(keys + slot);
         if (old == 0) {
             if (mz_load(flags + 2) > max_pairs) break;   // the table takes no new keys once it holds more than max_pairs (flags[1] is set below)
             old = atomicCAS(keys + slot, 0ull, key);
@@ -71,53 +64,30 @@ __device__ __forceinline__ void mz_pair_add(mz_u64 key, int n, mz_u64* __restric
             }
         }
         if (old == key) {
-            mz_add(counts + slot, n);
+            use(slot);
             return;
         }
     }
     mz_store(flags + 1, 1);
+}
+// the pair key of two neighbouring ids: smaller << 32 | larger, 0 (nothing to count) unless both are positive and differ
+__device__ __forceinline__ mz_u64 mz_pair_key(int a, int b) {
+    if (a <= 0 || b <= 0 || a == b) return 0;
+    return a < b ? ((mz_u64)a << 32) | (mz_u64)b : ((mz_u64)b << 32) | (mz_u64)a;
+}
+template <class CT>
+__device__ __forceinline__ void mz_pair_add(mz_u64 key, int n, mz_u64* __restrict__ keys, CT* __restrict__ counts, mz_u64 mask, int max_pairs,
+                                            int* __restrict__ flags) {
+    mz_pair_slot(key, keys, mask, max_pairs, flags, [&](mz_u64 slot) { mz_add(counts + slot, n); });
 }
 // The same table with three 64-bit counts per key, counts i64 [mask + 1, 3] (measure3d.hip: the faces two objects share, per axis): adds n at
 // 3 * slot + axis.
 __device__ __forceinline__ void mz_pair_add_axis(mz_u64 key, int axis, int n, mz_u64* __restrict__ keys, long* __restrict__ counts, mz_u64 mask,
                                                  int max_pairs, int* __restrict__ flags) {
-    mz_u64 slot = mz_hash(key) & mask;
-    for (mz_u64 probes = 0; probes <= mask; ++probes, slot = (slot + 1) & mask) {
-        mz_u64 old = __hip_atomic_load(keys + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == 0) {
-            if (mz_load(flags + 2) > max_pairs) break;
-            old = atomicCAS(keys + slot, 0ull, key);
-            if (old == 0) {
-                mz_add(flags + 2, 1);
-                old = key;
-            }
-        }
-        if (old == key) {
-            mz_add(counts + 3 * slot + axis, n);
-            return;
-        }
-    }
-    mz_store(flags + 1, 1);
+    mz_pair_slot(key, keys, mask, max_pairs, flags, [&](mz_u64 slot) { mz_add(counts + 3 * slot + axis, n); });
 }
-// The same table with a maximum per key instead of a sum (split.hip: the pass between two basins); vals are zeroed by the caller and v > 0.  The
-// atomic is sent only when a relaxed load says it improves.
+// The same table with a maximum per key instead of a sum (split.hip: the pass between two basins); vals are zeroed by the caller and v > 0.
 __device__ __forceinline__ void mz_pair_max(mz_u64 key, int v, mz_u64* __restrict__ keys, int* __restrict__ vals, mz_u64 mask, int max_pairs,
                                             int* __restrict__ flags) {
-    mz_u64 slot = mz_hash(key) & mask;
-    for (mz_u64 probes = 0; probes <= mask; ++probes, slot = (slot + 1) & mask) {
-        mz_u64 old = __hip_atomic_load(keys + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == 0) {
-            if (mz_load(flags + 2) > max_pairs) break;
-            old = atomicCAS(keys + slot, 0ull, key);
-            if (old == 0) {
-                mz_add(flags + 2, 1);
-                old = key;
-            }
-        }
-        if (old == key) {
-            if (mz_load(vals + slot) < v) mz_max(vals + slot, v);
-            return;
-        }
-    }
-    mz_store(flags + 1, 1);
+    mz_pair_slot(key, keys, mask, max_pairs, flags, [&](mz_u64 slot) { mz_send_max(vals + slot, v); });
 }

@@ -17,7 +17,7 @@
 // rows + row counts, never as a distance map.  The same pass sums x and y over M_i (the centroid of an instance without interior).
 // Points.  One wave per instance: a rank among the candidates in row-major order is found by a prefix scan over the row counts, then over the
 // popcounts of the row's words, then by clearing the lowest set bits of the word.  Ranks come from the draw rule (philox.h).
-#include "common.h"
+#include "label_common.h"   // the relaxed load
 #include "philox.h"
 #include <limits.h>
 
@@ -26,8 +26,6 @@
 #define PR_PTS 16           // num_pos, num_neg at most
 #define PR_TR 16            // rows of a tile
 #define PR_TILES 64         // blocks per instance in prompt_sets_kernel (each strides over the window's tiles)
-
-__device__ __forceinline__ int pr_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---- interior: truncated city-block distance to the nearest different label -------------------------------------------------------
 // grid (ceil(W / 256), min(H, 65535)), block 256
@@ -93,7 +91,7 @@ __global__ __launch_bounds__(256) void prompt_choose_kernel(const int* __restric
     __syncthreads();                                         // present[] is read below by other threads of this workgroup
     const int P = total_s;
     if (P <= max_inst) {
-        for (int j = t; j < P; j += 256) sel[j] = pr_load(present + j);
+        for (int j = t; j < P; j += 256) sel[j] = mz_load(present + j);
         if (t == 0) info[0] = P;
         return;
     }
@@ -105,7 +103,7 @@ __global__ __launch_bounds__(256) void prompt_choose_kernel(const int* __restric
         while (j < tt && sorted[j] <= r) { ++r; ++j; }
         for (int q = tt; q > j; --q) sorted[q] = sorted[q - 1];
         sorted[j] = r;
-        sel[tt] = pr_load(present + r);
+        sel[tt] = mz_load(present + r);
     }
     info[0] = max_inst;
 }
@@ -212,7 +210,7 @@ template <typename F> __device__ __forceinline__ int pr_find(int i0, int i1, lon
     for (int a = i0; a <= i1; a += 64) {
         const int i = a + lane;
         const long c = i <= i1 ? (long)cnt(i) : 0;
-        long inc = c;
+        long inc = c;                                    // (written out: wave_scan_incl() changes the callers' code)
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const long u = __shfl_up(inc, o, 64);

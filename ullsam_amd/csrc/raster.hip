@@ -19,7 +19,7 @@
 //            label by label and joins the parts of a label that goes on, so a label that fills them costs one atomic set.
 // flags i32 [4]: [0] = status bits: 1 = a ring_label outside 1..K, 2 = a coordinate beyond 65535 * 256, 4 = a total above 2^31 - 1, 8 = an index or a
 // value that left its table (skipped; nothing is indexed with it); [1] = C.
-#include "pair_table.h"
+#include "label_common.h"
 #include <stdint.h>
 
 #define RS_BLOCK 256
@@ -34,8 +34,6 @@
 #define RS_BAD_INDEX 8
 #define RS_INT_MAX 2147483647L
 
-__device__ __forceinline__ bool rs_in(long i, long n) { return i >= 0 && i < n; }
-__device__ __forceinline__ void rs_flag(int* flags, int bit) { (void)__hip_atomic_fetch_or(flags, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ bool rs_coord(int v) { return v >= -RS_LIMIT && v <= RS_LIMIT; }
 // ceil(a / 256) for either sign (>> on a negative int is the arithmetic shift)
 __device__ __forceinline__ int rs_ceil256(int a) { return (a + 255) >> 8; }
@@ -51,29 +49,7 @@ __device__ __forceinline__ long rs_find(const int* __restrict__ table, long n, l
 }
 
 // ---- scan -----------------------------------------------------------------------------------------------------------------------------------
-// the exclusive scan of v over the workgroup's RS_BLOCK threads; total = the sum over all of them
-template <class T> __device__ __forceinline__ T rs_block_exscan(T v, T& total) {
-    __shared__ T s_wave[RS_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    T inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    __syncthreads();                                      // (the table may still be read from an earlier call)
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (int i = 0; i < RS_BLOCK / 64; ++i) {
-        const T t = s_wave[i];
-        if (i < wave) before += t;
-        all += t;
-    }
-    total = all;
-    return before + inc - v;
-}
+// (block_exscan<RS_BLOCK>: label_common.h)
 // the RS_PER values of a thread, bounds checked; a value outside 0..32767 counts as 0 (a status bit): a block's sum stays below 2^26
 __device__ __forceinline__ int rs_take(const int* __restrict__ vals, long n, long i0, int (&c)[RS_PER], int* __restrict__ flags) {
     int sum = 0;
@@ -81,7 +57,7 @@ __device__ __forceinline__ int rs_take(const int* __restrict__ vals, long n, lon
     for (int j = 0; j < RS_PER; ++j) {
         int v = i0 + j < n ? vals[i0 + j] : 0;
         if (v < 0 || v > RS_MAX_SIDE) {
-            rs_flag(flags, RS_BAD_INDEX);
+            mz_or(flags, RS_BAD_INDEX);
             v = 0;
         }
         c[j] = v;
@@ -92,7 +68,7 @@ __device__ __forceinline__ int rs_take(const int* __restrict__ vals, long n, lon
 __global__ __launch_bounds__(RS_BLOCK) void raster_sums_kernel(const int* __restrict__ vals, long n, int* __restrict__ sums, int* __restrict__ flags) {
     int c[RS_PER], total;
     const int mine = rs_take(vals, n, (long)blockIdx.x * RS_CHUNK + (long)threadIdx.x * RS_PER, c, flags);
-    (void)rs_block_exscan<int>(mine, total);
+    (void)block_exscan<RS_BLOCK>(mine, total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 // one workgroup: sums[b] = the sum of the blocks before b; *total = the sum of all; either is held at 2^31 - 1, with a status bit, when it is larger
@@ -102,12 +78,12 @@ __global__ __launch_bounds__(RS_BLOCK) void raster_scan_sums_kernel(int* __restr
         const long i = base + threadIdx.x;
         const long v = i < nb ? (long)sums[i] : 0;
         long all;
-        const long ex = carry + rs_block_exscan<long>(v, all);
+        const long ex = carry + block_exscan<RS_BLOCK>(v, all);
         if (i < nb) sums[i] = (int)(ex < RS_INT_MAX ? ex : RS_INT_MAX);
         carry += all;
     }
     if (threadIdx.x == 0) {
-        if (carry > RS_INT_MAX) rs_flag(flags, RS_TOO_MANY);
+        if (carry > RS_INT_MAX) mz_or(flags, RS_TOO_MANY);
         mz_store(total, (int)(carry < RS_INT_MAX ? carry : RS_INT_MAX));
     }
 }
@@ -116,7 +92,7 @@ __global__ __launch_bounds__(RS_BLOCK) void raster_offsets_kernel(const int* __r
     int c[RS_PER], total;
     const long i0 = (long)blockIdx.x * RS_CHUNK + (long)threadIdx.x * RS_PER;
     const int mine = rs_take(vals, n, i0, c, flags);
-    long at = (long)sums[blockIdx.x] + rs_block_exscan<int>(mine, total);
+    long at = (long)sums[blockIdx.x] + block_exscan<RS_BLOCK>(mine, total);
 #pragma unroll
     for (int j = 0; j < RS_PER; ++j) {
         if (i0 + j < n) off[i0 + j] = (int)(at < RS_INT_MAX ? at : RS_INT_MAX);
@@ -134,16 +110,16 @@ __global__ __launch_bounds__(RS_BLOCK) void raster_edges_kernel(const int* __res
     const long s0 = start[r], s1 = start[r + 1];
     int r0 = 0, c = 0, lab = 0;
     long j = i;
-    if (!(s0 >= 0 && s0 <= i && i < s1 && s1 <= N)) rs_flag(flags, RS_BAD_INDEX);   // (a hand-made start)
+    if (!(s0 >= 0 && s0 <= i && i < s1 && s1 <= N)) mz_or(flags, RS_BAD_INDEX);   // (a hand-made start)
     else {
         j = i + 1 < s1 ? i + 1 : s0;
         lab = ring_label[r];
         const int x0 = q[2 * i], y0 = q[2 * i + 1], x1 = q[2 * j], y1 = q[2 * j + 1];
         if (lab < 1 || lab > K) {
-            rs_flag(flags, RS_BAD_LABEL);
+            mz_or(flags, RS_BAD_LABEL);
             lab = 0;
         } else if (!(rs_coord(x0) && rs_coord(y0) && rs_coord(x1) && rs_coord(y1))) {
-            rs_flag(flags, RS_BAD_COORD);
+            mz_or(flags, RS_BAD_COORD);
             lab = 0;
         } else {
             const int lo = max(rs_ceil256(min(y0, y1) - 128), 0), hi = min(rs_ceil256(max(y0, y1) - 128), H);
@@ -170,18 +146,18 @@ __global__ __launch_bounds__(RS_BLOCK) void raster_keys_kernel(const int* __rest
     const long t = c - (long)off[e], y = (long)row0[e] + t, j = nxt[e];
     const int lab = elab[e];
     long long key = 0;
-    if (!(t >= 0 && t < (long)cnt[e] && rs_in(y, H) && rs_in(j, N))) rs_flag(flags, RS_BAD_INDEX);
-    else if (lab < 1 || lab > K) rs_flag(flags, RS_BAD_LABEL);
+    if (!(t >= 0 && t < (long)cnt[e] && mz_in(y, H) && mz_in(j, N))) mz_or(flags, RS_BAD_INDEX);
+    else if (lab < 1 || lab > K) mz_or(flags, RS_BAD_LABEL);
     else {
         long x0 = q[2 * e], y0 = q[2 * e + 1], x1 = q[2 * j], y1 = q[2 * j + 1];
-        if (!(rs_coord((int)x0) && rs_coord((int)y0) && rs_coord((int)x1) && rs_coord((int)y1))) rs_flag(flags, RS_BAD_COORD);
+        if (!(rs_coord((int)x0) && rs_coord((int)y0) && rs_coord((int)x1) && rs_coord((int)y1))) mz_or(flags, RS_BAD_COORD);
         else {
             if (y0 > y1) {                                // the endpoints ordered by y: the value does not depend on the edge's direction
                 long s = x0; x0 = x1; x1 = s;
                 s = y0; y0 = y1; y1 = s;
             }
             const long cy = 256 * y + 128;
-            if (!(y0 <= cy && cy < y1)) rs_flag(flags, RS_BAD_INDEX);    // (a hand-made row0)
+            if (!(y0 <= cy && cy < y1)) mz_or(flags, RS_BAD_INDEX);    // (a hand-made row0)
             else {
                 const long d = y1 - y0, a = (x0 - 128) * d + (cy - y0) * (x1 - x0), b = 256 * d;    // |a| < 2^52
                 long xs = a / b;                          // truncates towards zero: the ceiling already where a < 0
@@ -204,7 +180,7 @@ __device__ __forceinline__ bool rs_span(const long long* __restrict__ keys, long
     xa = (int)a & 0xFFFF;
     xb = (int)b & 0xFFFF;
     const bool ok = a >= 0 && (a >> 16) == (b >> 16) && lab >= 1 && lab <= K && y < H && xa <= xb && xb <= W;
-    if (!ok) rs_flag(flags, RS_BAD_INDEX);
+    if (!ok) mz_or(flags, RS_BAD_INDEX);
     return ok;
 }
 // the wave merges its lanes label by label: one atomic for every distinct label of the wave, however the spans arrive.  Sums of integers: the
@@ -251,8 +227,8 @@ __global__ __launch_bounds__(RS_BLOCK) void raster_covered_kernel(const long lon
 // the value a span paints: its label's rank + 1, or 0 (a status bit) for a rank outside 0..K - 1
 __device__ __forceinline__ int rs_value(const int* __restrict__ rank, int lab, long K, int* __restrict__ flags) {
     const int rk = rank[lab - 1];
-    if (rs_in(rk, K)) return rk + 1;
-    rs_flag(flags, RS_BAD_INDEX);
+    if (mz_in(rk, K)) return rk + 1;
+    mz_or(flags, RS_BAD_INDEX);
     return 0;
 }
 // form 0: one wave per span, its lanes striding the pixels
@@ -278,7 +254,7 @@ __global__ __launch_bounds__(RS_BLOCK) void raster_paint_pixels_kernel(const lon
         if (!rs_span(keys, j, H, W, K, lab, y, xa, xb, flags)) continue;
         const long x = (long)xa + (t - (long)poff[j]);
         if (!(x >= xa && x < xb)) {                       // (a hand-made poff)
-            rs_flag(flags, RS_BAD_INDEX);
+            mz_or(flags, RS_BAD_INDEX);
             continue;
         }
         const int v = rs_value(rank, lab, K, flags);
@@ -347,11 +323,11 @@ __global__ __launch_bounds__(RS_BLOCK) void raster_finish_kernel(const int* __re
         const long p = base + 64 * s + lane;
         int l = 0;
         if (p < n) {
-            if (!rs_in(ls[s], K + 1)) rs_flag(flags, RS_BAD_INDEX);
+            if (!mz_in(ls[s], K + 1)) mz_or(flags, RS_BAD_INDEX);
             else {
                 l = label_of[ls[s]];
-                if (!rs_in(l, K + 1)) {
-                    rs_flag(flags, RS_BAD_INDEX);
+                if (!mz_in(l, K + 1)) {
+                    mz_or(flags, RS_BAD_INDEX);
                     l = 0;
                 }
             }
@@ -414,8 +390,6 @@ __global__ __launch_bounds__(RS_BLOCK) void raster_finish_kernel(const int* __re
         }                                                           \
     } while (0)
 
-static unsigned rs_blocks(long n) { return (unsigned)((n + RS_BLOCK - 1) / RS_BLOCK); }
-
 static int rs_scan(const int* vals, long n, int* off, int* sums, int* total, int* flags, hipStream_t s) {
     const long nb = (n + RS_CHUNK - 1) / RS_CHUNK;
     raster_sums_kernel<<<(unsigned)nb, RS_BLOCK, 0, s>>>(vals, n, sums, flags);
@@ -448,7 +422,7 @@ extern "C" int ullsam_raster_edges(const int* q, long N, const int* start, long 
         RS_MEMSET("raster_edges", flags + 1, 4);
         return 0;
     }
-    raster_edges_kernel<<<rs_blocks(N), RS_BLOCK, 0, s>>>(q, N, start, R, ring_label, H, K, row0, cnt, nxt, elab, flags);
+    raster_edges_kernel<<<mz_blocks(N, RS_BLOCK), RS_BLOCK, 0, s>>>(q, N, start, R, ring_label, H, K, row0, cnt, nxt, elab, flags);
     ULLSAM_LAUNCH_CHECK();
     return rs_scan(cnt, N, off, sums, flags + 1, flags, s);
 }
@@ -461,7 +435,7 @@ extern "C" int ullsam_raster_keys(const int* q, long N, const int* row0, const i
     RS_COUNT_CHECK("raster_keys", C);
     ULLSAM_CHECK(C == 0 || N >= 1, "raster_keys: crossings without an edge");
     if (C == 0) return 0;
-    raster_keys_kernel<<<rs_blocks(C), RS_BLOCK, 0, reinterpret_cast<hipStream_t>(stream)>>>(q, N, row0, cnt, nxt, elab, off, C, H, W, K, keys, flags);
+    raster_keys_kernel<<<mz_blocks(C, RS_BLOCK), RS_BLOCK, 0, reinterpret_cast<hipStream_t>(stream)>>>(q, N, row0, cnt, nxt, elab, off, C, H, W, K, keys, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -475,7 +449,7 @@ extern "C" int ullsam_raster_covered(const long long* keys, long C, int H, int W
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (K > 0) RS_MEMSET("raster_covered", covered, (size_t)K * 4);
     if (C == 0) return 0;
-    raster_covered_kernel<<<rs_blocks((C / 2 + RS_RUN - 1) / RS_RUN), RS_BLOCK, 0, s>>>(keys, C / 2, H, W, K, covered, len, flags);
+    raster_covered_kernel<<<mz_blocks((C / 2 + RS_RUN - 1) / RS_RUN, RS_BLOCK), RS_BLOCK, 0, s>>>(keys, C / 2, H, W, K, covered, len, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -492,7 +466,7 @@ extern "C" int ullsam_raster_paint(const long long* keys, long C, const int* ran
     RS_MEMSET("raster_paint", raw, (size_t)H * W * 4);
     const long S = C / 2;
     if (S == 0 || K == 0) return 0;
-    if (form == 0) raster_paint_waves_kernel<<<rs_blocks(S * 64), RS_BLOCK, 0, s>>>(keys, S, rank, H, W, K, raw, flags);
+    if (form == 0) raster_paint_waves_kernel<<<mz_blocks(S * 64, RS_BLOCK), RS_BLOCK, 0, s>>>(keys, S, rank, H, W, K, raw, flags);
     else raster_paint_pixels_kernel<<<2048, RS_BLOCK, 0, s>>>(keys, S, rank, poff, total, H, W, K, raw, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
@@ -504,10 +478,10 @@ extern "C" int ullsam_raster_finish(const int* raw, int H, int W, const int* lab
     RS_IDS_CHECK("raster_finish");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (K > 0) {
-        raster_init_kernel<<<rs_blocks(K), RS_BLOCK, 0, s>>>(K, area, box);
+        raster_init_kernel<<<mz_blocks(K, RS_BLOCK), RS_BLOCK, 0, s>>>(K, area, box);
         ULLSAM_LAUNCH_CHECK();
     }
-    raster_finish_kernel<<<rs_blocks(((long)H * W + RS_SEGS - 1) / RS_SEGS), RS_BLOCK, 0, s>>>(raw, H, W, label_of, K, labels, area, box, flags);
+    raster_finish_kernel<<<mz_blocks(((long)H * W + RS_SEGS - 1) / RS_SEGS, RS_BLOCK), RS_BLOCK, 0, s>>>(raw, H, W, label_of, K, labels, area, box, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }

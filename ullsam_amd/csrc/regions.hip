@@ -17,7 +17,7 @@
 // joined edges does not depend on the order of the joins, so the parallel result is the sequential one.
 // Areas.  Integer atomicAdd into a per-root counter, one add per run of equal labels of a 64-pixel segment, and one add per
 // wave for a run that spans whole segments (a 2048^2 background region costs 2048 adds, not 4 M).
-#include "common.h"
+#include "label_common.h"   // the relaxed atomics, the global union-find
 
 #define RG_TW 64
 #define RG_TH 32
@@ -85,29 +85,6 @@ __global__ __launch_bounds__(256) void label_tile_kernel(const unsigned char* __
     }
 }
 
-__device__ __forceinline__ int rg_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int rg_min(int* p, int v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int rg_find_glb(const int* L, int i) {
-    int q = rg_load(L + i);
-    while (q != i) { i = q; q = rg_load(L + i); }
-    return i;
-}
-__device__ __forceinline__ void rg_union_glb(int* L, int a, int b) {
-    const int a0 = a, b0 = b;
-    for (;;) {
-        a = rg_find_glb(L, a);
-        b = rg_find_glb(L, b);
-        if (a == b) break;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = rg_min(L + a, b);
-        if (old == a) { a = b; break; }
-        a = old;
-    }
-    // shorten the two starting pixels' chains: `a` is an ancestor of both, and an atomicMin can only move a parent down
-    if (a < a0) rg_min(L + a0, a);
-    if (a < b0) rg_min(L + b0, a);
-}
-
 // One thread per pixel of a tile's top row (y % TH == 0, y > 0: joins N, else NW and NE) or left column (x % TW == 0, x > 0:
 // joins W, else NW and SW -- SW's edge to this pixel is SW's own NE edge, needed when SW has no N, i.e. no W here); a pair of
 // pixels that crosses both borders has its lower pixel on a top row.  grid (ceil(border pixels / 256), N).
@@ -118,25 +95,25 @@ __global__ __launch_bounds__(256) void label_merge_kernel(int H, int W, int nhb,
     if (t < nh) {
         const int y = (int)(t / W + 1) * RG_TH, x = (int)(t % W);
         const int p = y * W + x;
-        if (rg_load(L + p) < 0) return;
+        if (mz_load(L + p) < 0) return;
         const int q = p - W;
-        if (rg_load(L + q) >= 0) {
-            rg_union_glb(L, p, q);
+        if (mz_load(L + q) >= 0) {
+            mz_union(L, p, q);
         } else {
-            if (x > 0 && rg_load(L + q - 1) >= 0) rg_union_glb(L, p, q - 1);
-            if (x < W - 1 && rg_load(L + q + 1) >= 0) rg_union_glb(L, p, q + 1);
+            if (x > 0 && mz_load(L + q - 1) >= 0) mz_union(L, p, q - 1);
+            if (x < W - 1 && mz_load(L + q + 1) >= 0) mz_union(L, p, q + 1);
         }
     } else if (t < nh + (long)nvb * H) {
         const long u = t - nh;
         const int x = (int)(u / H + 1) * RG_TW, y = (int)(u % H);
         const int p = y * W + x;
-        if (rg_load(L + p) < 0) return;
+        if (mz_load(L + p) < 0) return;
         const int q = p - 1;
-        if (rg_load(L + q) >= 0) {
-            rg_union_glb(L, p, q);
+        if (mz_load(L + q) >= 0) {
+            mz_union(L, p, q);
         } else {
-            if (y > 0 && rg_load(L + q - W) >= 0) rg_union_glb(L, p, q - W);
-            if (y < H - 1 && rg_load(L + q + W) >= 0) rg_union_glb(L, p, q + W);
+            if (y > 0 && mz_load(L + q - W) >= 0) mz_union(L, p, q - W);
+            if (y < H - 1 && mz_load(L + q + W) >= 0) mz_union(L, p, q + W);
         }
     }
 }
@@ -331,7 +308,7 @@ __global__ __launch_bounds__(256) void rle_expand_kernel(const int* __restrict__
             loc[j] = tsum;
             tsum += c;
         }
-        long inc = tsum;                                 // inclusive wave scan of the threads' sums
+        long inc = tsum;                                 // inclusive wave scan of the threads' sums (written out: wave_scan_incl() changes this kernel's code)
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const long u = __shfl_up(inc, o, 64);

@@ -18,21 +18,12 @@
 //               for a block of rounds at a time; the rounds after one that kept nothing return at once.
 //   rings       the kept candidates in order are the vertices; nvert and area2 (the shoelace sum over the ring) per loop.
 // flags i32 [4]: [0] = an index that left its table (skipped; nothing is indexed with it); the others are free.
-#include "pair_table.h"
+#include "label_common.h"
 #include <stdint.h>
 
 #define SM_BLOCK 256
 #define SM_NONE 0xFFFFFFFFFFFFFFFFull
 
-__device__ __forceinline__ bool sm_in(long i, long n) { return i >= 0 && i < n; }
-__device__ __forceinline__ mz_u64 sm_load(const mz_u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// the atomic is sent only when a relaxed load says it improves: most arrivals at a busy address leave without one
-__device__ __forceinline__ void sm_max(mz_u64* p, mz_u64 v) {
-    if (sm_load(p) < v) (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void sm_min(mz_u64* p, mz_u64 v) {
-    if (sm_load(p) > v) (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ __forceinline__ int sm_x(int yx) { return yx & 0xFFFF; }
 __device__ __forceinline__ int sm_y(int yx) { return yx >> 16; }
 __device__ __forceinline__ long long sm_d2(int p, int q) {
@@ -85,7 +76,7 @@ __global__ __launch_bounds__(SM_BLOCK) void simplify_candidates_kernel(const int
         if ((long)estart[mid] <= i) lo = mid;
         else hi = mid;
     }
-    if (!sm_in(at, C) || t < 0 || (long)estart[lo] > i) {
+    if (!mz_in(at, C) || t < 0 || (long)estart[lo] > i) {
         mz_store(flags + 0, 1);
         return;
     }
@@ -99,7 +90,7 @@ __global__ __launch_bounds__(SM_BLOCK) void simplify_candidates_kernel(const int
 // the loop of candidate i when it has no fixed point, else -1
 __device__ __forceinline__ int sm_free_loop(const int* __restrict__ cloop, const int* __restrict__ nfixed, long L, long i, int* __restrict__ flags) {
     const int l = cloop[i];
-    if (!sm_in(l, L)) {
+    if (!mz_in(l, L)) {
         mz_store(flags + 0, 1);
         return -1;
     }
@@ -111,7 +102,7 @@ __global__ __launch_bounds__(SM_BLOCK) void simplify_anchor_first_kernel(const i
     const long i = (long)blockIdx.x * SM_BLOCK + threadIdx.x;
     if (i >= C) return;
     const int l = sm_free_loop(cloop, nfixed, L, i, flags);
-    if (l >= 0) sm_min(amin + l, (mz_u64)(unsigned)cxy[i] << 32 | (mz_u64)(unsigned)i);
+    if (l >= 0) mz_send_min(amin + l, (mz_u64)(unsigned)cxy[i] << 32 | (mz_u64)(unsigned)i);
 }
 __global__ __launch_bounds__(SM_BLOCK) void simplify_anchor_far_kernel(const int* __restrict__ cxy, const int* __restrict__ cloop,
                                                                        const int* __restrict__ nfixed, long C, long L, const mz_u64* __restrict__ amin,
@@ -121,7 +112,7 @@ __global__ __launch_bounds__(SM_BLOCK) void simplify_anchor_far_kernel(const int
     const int l = sm_free_loop(cloop, nfixed, L, i, flags);
     if (l < 0) return;
     const int first = (int)(amin[l] >> 32);               // (this loop's candidates all went through the first pass)
-    sm_max(amax + l, (mz_u64)sm_d2(cxy[i], first) << 32 | (mz_u64)(0xFFFFFFFFu - (unsigned)cxy[i]));
+    mz_send_max(amax + l, (mz_u64)sm_d2(cxy[i], first) << 32 | (mz_u64)(0xFFFFFFFFu - (unsigned)cxy[i]));
 }
 __global__ __launch_bounds__(SM_BLOCK) void simplify_anchor_mark_kernel(const int* __restrict__ cxy, const int* __restrict__ cloop,
                                                                         const int* __restrict__ nfixed, long C, long L, const mz_u64* __restrict__ amin,
@@ -141,12 +132,12 @@ __global__ __launch_bounds__(SM_BLOCK) void simplify_list_kernel(const unsigned 
     const long i = (long)blockIdx.x * SM_BLOCK + threadIdx.x;
     if (i >= C || !kept[i]) return;
     const long at = koff[i], n = total[0];
-    if (sm_in(at, n) && n <= C) klist[at] = (int)i;
+    if (mz_in(at, n) && n <= C) klist[at] = (int)i;
     else mz_store(flags + 0, 1);
 }
 // the kept candidates of loop l are klist[k0 : k1]; false when the tables do not fit (a hand-made table)
 __device__ __forceinline__ bool sm_span(const int* __restrict__ cstart, const int* __restrict__ koff, long C, long L, long n, int l, long& k0, long& k1) {
-    if (!sm_in(l, L)) return false;
+    if (!mz_in(l, L)) return false;
     const long cs = cstart[l], ce = cstart[l + 1];
     if (!(cs >= 0 && cs < ce && ce <= C)) return false;
     k0 = koff[cs];
@@ -166,7 +157,7 @@ __global__ __launch_bounds__(SM_BLOCK) void simplify_segments_kernel(const unsig
         if (sm_span(cstart, koff, C, L, n, cloop[i], k0, k1) && r >= k0 && r <= k1) {
             a = klist[r > k0 ? r - 1 : k1 - 1];
             b = klist[r < k1 ? r : k0];
-            if (!sm_in(a, C) || !sm_in(b, C)) a = b = -1;
+            if (!mz_in(a, C) || !mz_in(b, C)) a = b = -1;
         }
         if (a < 0) mz_store(flags + 0, 1);
     }
@@ -193,10 +184,10 @@ __global__ __launch_bounds__(SM_BLOCK) void simplify_round_max_kernel(const int*
     const long i = (long)blockIdx.x * SM_BLOCK + threadIdx.x;
     if (i >= C || sm_idle(prev)) return;
     const int a = pa[i], b = pb[i];
-    if (!sm_in(a, C) || !sm_in(b, C)) return;             // closed, kept, or never opened
+    if (!mz_in(a, C) || !mz_in(b, C)) return;             // closed, kept, or never opened
     const mz_u64 num = sm_num(cxy[i], cxy[a], cxy[b]);
     cnum[i] = num;
-    sm_min(segmax + a, ~num);                             // (the complement under a minimum: both tables start as all ones, one memset)
+    mz_send_min(segmax + a, ~num);                             // (the complement under a minimum: both tables start as all ones, one memset)
 }
 __global__ __launch_bounds__(SM_BLOCK) void simplify_round_win_kernel(const int* __restrict__ cxy, const int* __restrict__ pa, const int* __restrict__ pb,
                                                                       long C, long long T2, const int* __restrict__ prev,
@@ -205,12 +196,12 @@ __global__ __launch_bounds__(SM_BLOCK) void simplify_round_win_kernel(const int*
     const long i = (long)blockIdx.x * SM_BLOCK + threadIdx.x;
     if (i >= C || sm_idle(prev)) return;
     const int a = pa[i], b = pb[i];
-    if (!sm_in(a, C) || !sm_in(b, C)) return;
+    if (!mz_in(a, C) || !mz_in(b, C)) return;
     const mz_u64 num = cnum[i];
     if (~num != segmax[a]) return;
     const long long len = sm_d2(cxy[a], cxy[b]);
     const mz_u64 bound = ((mz_u64)T2 * (mz_u64)(len == 0 ? 1 : len)) >> 16;   // T2 < 2^32, len < 2^31
-    if (num > bound) sm_min(segwin + a, (mz_u64)(unsigned)cxy[i] << 32 | (mz_u64)(unsigned)i);
+    if (num > bound) mz_send_min(segwin + a, (mz_u64)(unsigned)cxy[i] << 32 | (mz_u64)(unsigned)i);
 }
 __global__ __launch_bounds__(SM_BLOCK) void simplify_round_mark_kernel(const int* __restrict__ cloop, const int* __restrict__ cstart, long C, long L,
                                                                        const int* __restrict__ prev, const mz_u64* __restrict__ segwin,
@@ -220,7 +211,7 @@ __global__ __launch_bounds__(SM_BLOCK) void simplify_round_mark_kernel(const int
     bool won = false;
     if (i < C && !sm_idle(prev)) {
         const int a = pa[i];
-        if (sm_in(a, C) && sm_in(pb[i], C)) {
+        if (mz_in(a, C) && mz_in(pb[i], C)) {
             const mz_u64 w = segwin[a];
             const long wi = (long)(w & 0xFFFFFFFFull);
             const int l = cloop[i];
@@ -229,7 +220,7 @@ __global__ __launch_bounds__(SM_BLOCK) void simplify_round_mark_kernel(const int
                 kept[i] = 1;
                 pa[i] = -1;
                 won = true;
-            } else if (!sm_in(wi, C) || !sm_in(l, L)) {
+            } else if (!mz_in(wi, C) || !mz_in(l, L)) {
                 mz_store(flags + 0, 1);
                 pa[i] = -1;
             } else {
@@ -261,7 +252,7 @@ __global__ __launch_bounds__(SM_BLOCK) void simplify_rings_kernel(const int* __r
         return;
     }
     const int j = klist[r + 1 < k1 ? r + 1 : k0];
-    if (!sm_in(j, C)) {
+    if (!mz_in(j, C)) {
         mz_store(flags + 0, 1);
         return;
     }
@@ -269,7 +260,7 @@ __global__ __launch_bounds__(SM_BLOCK) void simplify_rings_kernel(const int* __r
     vertices[2 * r + 0] = sm_x(p);
     vertices[2 * r + 1] = sm_y(p);
     mz_add(nvert + l, 1);
-    (void)__hip_atomic_fetch_add(area2 + l, (long long)sm_x(p) * sm_y(q) - (long long)sm_x(q) * sm_y(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    mz_add64(area2 + l, (mz_u64)((long long)sm_x(p) * sm_y(q) - (long long)sm_x(q) * sm_y(p)));
 }
 
 // ---- C ABI ------------------------------------------------------------------------------------------------------------------------------------
@@ -286,14 +277,12 @@ __global__ __launch_bounds__(SM_BLOCK) void simplify_rings_kernel(const int* __r
         }                                                           \
     } while (0)
 
-static unsigned sm_blocks(long n) { return (unsigned)((n + SM_BLOCK - 1) / SM_BLOCK); }
-
 extern "C" int ullsam_simplify_flags(const int* labels, int H, int W, const int* reid, const unsigned char* corner, long E, unsigned char* cand, int* flags,
                                      void* stream) {
     SM_FRAME_CHECK("simplify_flags");
     ULLSAM_CHECK(E >= 0 && E < 4 * SM_MAX_PIXELS, "simplify_flags: need 0 <= E < 2^31");
     if (E == 0) return 0;
-    simplify_flags_kernel<<<sm_blocks(E), SM_BLOCK, 0, reinterpret_cast<hipStream_t>(stream)>>>(labels, H, W, reid, corner, E, cand, flags);
+    simplify_flags_kernel<<<mz_blocks(E, SM_BLOCK), SM_BLOCK, 0, reinterpret_cast<hipStream_t>(stream)>>>(labels, H, W, reid, corner, E, cand, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -309,7 +298,7 @@ extern "C" int ullsam_simplify_candidates(const int* reid, const unsigned char* 
     SM_MEMSET(kept, 0, (size_t)C, "simplify_candidates");
     SM_MEMSET(cloop, 0xFF, (size_t)C * 4, "simplify_candidates");   // (a slot a hand-made table leaves out belongs to no loop)
     SM_MEMSET(cxy, 0, (size_t)C * 4, "simplify_candidates");
-    simplify_candidates_kernel<<<sm_blocks(E), SM_BLOCK, 0, s>>>(reid, cand, coff, estart, E, L, C, H, W, cxy, cloop, kept, nfixed, flags);
+    simplify_candidates_kernel<<<mz_blocks(E, SM_BLOCK), SM_BLOCK, 0, s>>>(reid, cand, coff, estart, E, L, C, H, W, cxy, cloop, kept, nfixed, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -324,11 +313,11 @@ extern "C" int ullsam_simplify_anchors(const int* cxy, const int* cloop, const i
     mz_u64* amax = amin + L;
     SM_MEMSET(amin, 0xFF, (size_t)L * 8, "simplify_anchors");
     SM_MEMSET(amax, 0, (size_t)L * 8, "simplify_anchors");
-    simplify_anchor_first_kernel<<<sm_blocks(C), SM_BLOCK, 0, s>>>(cxy, cloop, nfixed, C, L, amin, flags);
+    simplify_anchor_first_kernel<<<mz_blocks(C, SM_BLOCK), SM_BLOCK, 0, s>>>(cxy, cloop, nfixed, C, L, amin, flags);
     ULLSAM_LAUNCH_CHECK();
-    simplify_anchor_far_kernel<<<sm_blocks(C), SM_BLOCK, 0, s>>>(cxy, cloop, nfixed, C, L, amin, amax, flags);
+    simplify_anchor_far_kernel<<<mz_blocks(C, SM_BLOCK), SM_BLOCK, 0, s>>>(cxy, cloop, nfixed, C, L, amin, amax, flags);
     ULLSAM_LAUNCH_CHECK();
-    simplify_anchor_mark_kernel<<<sm_blocks(C), SM_BLOCK, 0, s>>>(cxy, cloop, nfixed, C, L, amin, amax, kept, flags);
+    simplify_anchor_mark_kernel<<<mz_blocks(C, SM_BLOCK), SM_BLOCK, 0, s>>>(cxy, cloop, nfixed, C, L, amin, amax, kept, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -340,9 +329,9 @@ extern "C" int ullsam_simplify_segments(const unsigned char* kept, const int* ko
     if (C == 0) return 0;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     SM_MEMSET(klist, 0xFF, (size_t)C * 4, "simplify_segments");
-    simplify_list_kernel<<<sm_blocks(C), SM_BLOCK, 0, s>>>(kept, koff, C, total, klist, flags);
+    simplify_list_kernel<<<mz_blocks(C, SM_BLOCK), SM_BLOCK, 0, s>>>(kept, koff, C, total, klist, flags);
     ULLSAM_LAUNCH_CHECK();
-    simplify_segments_kernel<<<sm_blocks(C), SM_BLOCK, 0, s>>>(kept, koff, cloop, cstart, C, L, total, klist, pa, pb, flags);
+    simplify_segments_kernel<<<mz_blocks(C, SM_BLOCK), SM_BLOCK, 0, s>>>(kept, koff, cloop, cstart, C, L, total, klist, pa, pb, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -361,11 +350,11 @@ extern "C" int ullsam_simplify_rounds(const int* cxy, const int* cloop, const in
     for (int r = 0; r < rounds; ++r) {
         const int* prev = r ? counts + r - 1 : nullptr;
         SM_MEMSET(segmax, 0xFF, (size_t)C * 16, "simplify_rounds");   // segmax and segwin, one after the other
-        simplify_round_max_kernel<<<sm_blocks(C), SM_BLOCK, 0, s>>>(cxy, pa, pb, C, prev, cnum, segmax);
+        simplify_round_max_kernel<<<mz_blocks(C, SM_BLOCK), SM_BLOCK, 0, s>>>(cxy, pa, pb, C, prev, cnum, segmax);
         ULLSAM_LAUNCH_CHECK();
-        simplify_round_win_kernel<<<sm_blocks(C), SM_BLOCK, 0, s>>>(cxy, pa, pb, C, T2, prev, cnum, segmax, segwin);
+        simplify_round_win_kernel<<<mz_blocks(C, SM_BLOCK), SM_BLOCK, 0, s>>>(cxy, pa, pb, C, T2, prev, cnum, segmax, segwin);
         ULLSAM_LAUNCH_CHECK();
-        simplify_round_mark_kernel<<<sm_blocks(C), SM_BLOCK, 0, s>>>(cloop, cstart, C, L, prev, segwin, pa, pb, kept, counts + r, flags);
+        simplify_round_mark_kernel<<<mz_blocks(C, SM_BLOCK), SM_BLOCK, 0, s>>>(cloop, cstart, C, L, prev, segwin, pa, pb, kept, counts + r, flags);
         ULLSAM_LAUNCH_CHECK();
     }
     return 0;
@@ -382,9 +371,9 @@ extern "C" int ullsam_simplify_rings(const int* cxy, const int* cloop, const uns
     SM_MEMSET(area2, 0, (size_t)L * 8, "simplify_rings");
     if (C == 0 || N == 0) return 0;
     SM_MEMSET(klist, 0xFF, (size_t)C * 4, "simplify_rings");
-    simplify_list_kernel<<<sm_blocks(C), SM_BLOCK, 0, s>>>(kept, voff, C, total, klist, flags);
+    simplify_list_kernel<<<mz_blocks(C, SM_BLOCK), SM_BLOCK, 0, s>>>(kept, voff, C, total, klist, flags);
     ULLSAM_LAUNCH_CHECK();
-    simplify_rings_kernel<<<sm_blocks(C), SM_BLOCK, 0, s>>>(cxy, cloop, kept, voff, cstart, C, L, N, total, klist, vertices, nvert, area2, flags);
+    simplify_rings_kernel<<<mz_blocks(C, SM_BLOCK), SM_BLOCK, 0, s>>>(cxy, cloop, kept, voff, cstart, C, L, N, total, klist, vertices, nvert, area2, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }

@@ -26,8 +26,6 @@
 #define SP_TH 4
 #define SP_BLOCK (SP_TW * SP_TH)
 
-__device__ __forceinline__ bool sp_live(int l, long K) { return l > 0 && l <= K; }
-
 // ---- ascent ---------------------------------------------------------------------------------------------------------------------------------
 // grid (ceil(W / SP_TW), ceil(H / SP_TH)), block SP_BLOCK
 template <bool LDS>
@@ -51,7 +49,7 @@ __global__ __launch_bounds__(SP_BLOCK) void split_ascent_kernel(const int* __res
     if (x >= W || y >= H) return;
     const int p = y * W + x;                              // H * W < 2^30
     const int l = labels[p];
-    if (!sp_live(l, K)) {
+    if (!mz_live(l, K)) {
         if (l != 0) mz_store(flags + 0, 1);
         up[p] = p;
         return;
@@ -113,7 +111,7 @@ __global__ __launch_bounds__(256) void split_passes_kernel(const int* __restrict
     if (x >= W) return;
     const int p = y * W + x;
     const int l = labels[p];
-    if (!sp_live(l, K)) return;
+    if (!mz_live(l, K)) return;
     const int dp = d2[p];
     const unsigned rp = (unsigned)up[p];
 #pragma unroll
@@ -131,10 +129,6 @@ __global__ __launch_bounds__(256) void split_passes_kernel(const int* __restrict
 }
 
 // ---- one round of merging -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void sp_best(mz_u64* slot, mz_u64 word) {
-    if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < word)
-        (void)__hip_atomic_fetch_max(slot, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 // one thread per slot; up is flattened: up[a] is the representative of a's component
 __global__ __launch_bounds__(256) void split_best_kernel(const mz_u64* __restrict__ keys, const int* __restrict__ vals, long cap, const int* __restrict__ up,
                                                          long n, mz_u64* __restrict__ best, int* __restrict__ flags) {
@@ -150,15 +144,15 @@ __global__ __launch_bounds__(256) void split_best_kernel(const mz_u64* __restric
     }
     const unsigned X = (unsigned)up[a], Y = (unsigned)up[b];
     if (X == Y || X >= n || Y >= n) return;
-    sp_best(best + X, ((mz_u64)(unsigned)s << 32) | (mz_u64)(0xFFFFFFFFu - Y));
-    sp_best(best + Y, ((mz_u64)(unsigned)s << 32) | (mz_u64)(0xFFFFFFFFu - X));
+    mz_send_max(best + X, ((mz_u64)(unsigned)s << 32) | (mz_u64)(0xFFFFFFFFu - Y));
+    mz_send_max(best + Y, ((mz_u64)(unsigned)s << 32) | (mz_u64)(0xFFFFFFFFu - X));
 }
 // one thread per pixel; only a root reads and clears its own word and writes its own pointer
 __global__ __launch_bounds__(256) void split_decide_kernel(const int* __restrict__ labels, const int* __restrict__ d2, long n, long K, long h,
                                                            mz_u64* __restrict__ best, int* __restrict__ up, int* __restrict__ changed) {
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
-    if (!sp_live(labels[p], K) || up[p] != (int)p) return;
+    if (!mz_live(labels[p], K) || up[p] != (int)p) return;
     const mz_u64 w = best[p];
     if (w == 0) return;
     best[p] = 0;
@@ -183,7 +177,7 @@ __global__ __launch_bounds__(256) void split_collect_kernel(const int* __restric
     bool rep = false;
     if (p < n) {
         l = labels[p];
-        rep = sp_live(l, K) && up[p] == (int)p;
+        rep = mz_live(l, K) && up[p] == (int)p;
     }
     const mz_u64 m = __ballot(rep);
     if (m == 0) return;                                   // wave-uniform
@@ -224,7 +218,7 @@ __global__ __launch_bounds__(256) void split_relabel_kernel(const int* __restric
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
     int v = 0;
-    if (sp_live(labels[p], K)) {
+    if (mz_live(labels[p], K)) {
         const int r = up[p];
         if (r >= 0 && r < n) v = newid[r];
     }
@@ -236,8 +230,6 @@ __global__ __launch_bounds__(256) void split_relabel_kernel(const int* __restric
     ULLSAM_CHECK(H >= 1 && H <= 32767 && W >= 1 && W <= 32767 && K >= 0 && K <= 2147483647L, what ": need 1 <= H, W <= 32767 and 0 <= K <= 2^31 - 1")
 #define SP_FLAT_CHECK(what) \
     ULLSAM_CHECK(n >= 1 && n <= 32767L * 32767L && K >= 0 && K <= 2147483647L, what ": need 1 <= n <= 32767^2 and 0 <= K <= 2^31 - 1")
-
-static unsigned sp_blocks(long n) { return (unsigned)((n + 255) / 256); }
 
 extern "C" int ullsam_split_ascent(const int* labels, const int* d2, int H, int W, long K, int route, int* up, int* flags, void* stream) {
     SP_FRAME_CHECK("split_ascent");
@@ -252,7 +244,7 @@ extern "C" int ullsam_split_ascent(const int* labels, const int* d2, int H, int 
 
 extern "C" int ullsam_split_flatten(int* up, long n, long steps, int* flags, void* stream) {
     ULLSAM_CHECK(n >= 1 && n <= 32767L * 32767L && steps >= 0 && steps <= n, "split_flatten: need 1 <= n <= 32767^2 and 0 <= steps <= n");
-    split_flatten_kernel<<<sp_blocks(n), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(n, steps, up, flags);
+    split_flatten_kernel<<<mz_blocks(n), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(n, steps, up, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -262,7 +254,7 @@ extern "C" int ullsam_split_passes(const int* labels, const int* d2, const int* 
     SP_FRAME_CHECK("split_passes");
     ULLSAM_CHECK(cap >= 2 && (cap & (cap - 1)) == 0 && max_pairs >= 1 && 2L * max_pairs <= cap, "split_passes: cap must be a power of two >= 2 * max_pairs");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(keys, 0, (size_t)cap * 8, s) != hipSuccess || hipMemsetAsync(vals, 0, (size_t)cap * 4, s) != hipSuccess) {
+    if (!mz_zero(keys, (size_t)cap * 8, s) || !mz_zero(vals, (size_t)cap * 4, s)) {
         ullsam_set_error("split_passes: memset failed");
         return -2;
     }
@@ -278,9 +270,9 @@ extern "C" int ullsam_split_round(const unsigned long long* keys, const int* val
     ULLSAM_CHECK(cap >= 0 && h >= 0 && h <= 32767, "split_round: need cap >= 0 and 0 <= h <= 32767");
     if (cap == 0) return 0;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    split_best_kernel<<<sp_blocks(cap), 256, 0, s>>>(reinterpret_cast<const mz_u64*>(keys), vals, cap, up, n, reinterpret_cast<mz_u64*>(best), flags);
+    split_best_kernel<<<mz_blocks(cap), 256, 0, s>>>(reinterpret_cast<const mz_u64*>(keys), vals, cap, up, n, reinterpret_cast<mz_u64*>(best), flags);
     ULLSAM_LAUNCH_CHECK();
-    split_decide_kernel<<<sp_blocks(n), 256, 0, s>>>(labels, d2, n, K, (long)h, reinterpret_cast<mz_u64*>(best), up, changed);
+    split_decide_kernel<<<mz_blocks(n), 256, 0, s>>>(labels, d2, n, K, (long)h, reinterpret_cast<mz_u64*>(best), up, changed);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -288,7 +280,7 @@ extern "C" int ullsam_split_round(const unsigned long long* keys, const int* val
 extern "C" int ullsam_split_collect(const int* labels, const int* up, long n, long K, unsigned long long* list, long room, int* flags, void* stream) {
     SP_FLAT_CHECK("split_collect");
     ULLSAM_CHECK(room >= 0 && (list != nullptr || room == 0), "split_collect: room >= 0, and 0 without a list");
-    split_collect_kernel<<<sp_blocks(n), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(labels, up, n, K, reinterpret_cast<mz_u64*>(list), room, flags);
+    split_collect_kernel<<<mz_blocks(n), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(labels, up, n, K, reinterpret_cast<mz_u64*>(list), room, flags);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -299,16 +291,16 @@ extern "C" int ullsam_split_relabel(const unsigned long long* list, long parts, 
     ULLSAM_CHECK(parts >= 0 && parts <= (long)H * W && K <= 2147483646L, "split_relabel: need 0 <= parts <= H * W and K <= 2^31 - 2");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const long n = (long)H * W;
-    if (K > 0 && hipMemsetAsync(parts_of, 0, (size_t)K * 4, s) != hipSuccess) {
+    if (!mz_zero(parts_of, (size_t)K * 4, s)) {
         ullsam_set_error("split_relabel: memset failed");
         return -2;
     }
     if (parts > 0) {
-        split_tables_kernel<<<sp_blocks(parts), 256, 0, s>>>(reinterpret_cast<const mz_u64*>(list), parts, d2, n, W, K, newid, parent, peak_r2, peak_xy, parts_of,
+        split_tables_kernel<<<mz_blocks(parts), 256, 0, s>>>(reinterpret_cast<const mz_u64*>(list), parts, d2, n, W, K, newid, parent, peak_r2, peak_xy, parts_of,
                                                              flags);
         ULLSAM_LAUNCH_CHECK();
     }
-    split_relabel_kernel<<<sp_blocks(n), 256, 0, s>>>(labels, up, newid, n, K, out);
+    split_relabel_kernel<<<mz_blocks(n), 256, 0, s>>>(labels, up, newid, n, K, out);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }

@@ -25,8 +25,6 @@
 #define S3_TZ 4
 #define S3_BLOCK (S3_TX * S3_TY)
 
-__device__ __forceinline__ bool s3_live(int l, long K) { return l > 0 && l <= K; }
-
 // ---- ascent ---------------------------------------------------------------------------------------------------------------------------------
 // grid (ceil(W / S3_TX), ceil(H / S3_TY), ceil(Z / S3_TZ)), block S3_BLOCK
 template <bool LDS>
@@ -57,7 +55,7 @@ __global__ __launch_bounds__(S3_BLOCK) void split3_ascent_kernel(const int* __re
         const int p = z * HW + y * W + x;
         const int c = ((lz + 1) * LH + (ly + 1)) * LW + (lx + 1);
         const int l = LDS ? s_lab[c] : labels[p];
-        if (!s3_live(l, K)) {
+        if (!mz_live(l, K)) {
             if (l != 0) mz_store(flags + 0, 1);
             up[p] = p;
             continue;
@@ -125,7 +123,7 @@ __global__ __launch_bounds__(S3_BLOCK) void split3_passes_kernel(const int* __re
         if (z0 + lz >= Z) break;
         const int c = (lz * LH + (ly + 1)) * LW + (lx + 1);
         const int l = s_lab[c];
-        if (!s3_live(l, K)) continue;
+        if (!mz_live(l, K)) continue;
         const int dp = s_d2[c];
         const unsigned rp = (unsigned)s_up[c];
 #pragma unroll
@@ -181,7 +179,7 @@ __global__ __launch_bounds__(256) void split3_relabel_kernel(const int* __restri
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
     int v = 0;
-    if (s3_live(labels[p], K)) {
+    if (mz_live(labels[p], K)) {
         const int r = up[p];
         if (r >= 0 && r < n) v = newid[r];
     }
@@ -209,7 +207,7 @@ extern "C" int ullsam_split3d_passes(const int* labels, const int* d2, const int
     S3_VOLUME_CHECK("split3d_passes");
     ULLSAM_CHECK(cap >= 2 && (cap & (cap - 1)) == 0 && max_pairs >= 1 && 2L * max_pairs <= cap, "split3d_passes: cap must be a power of two >= 2 * max_pairs");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(keys, 0, (size_t)cap * 8, s) != hipSuccess || hipMemsetAsync(vals, 0, (size_t)cap * 4, s) != hipSuccess) {
+    if (!mz_zero(keys, (size_t)cap * 8, s) || !mz_zero(vals, (size_t)cap * 4, s)) {
         ullsam_set_error("split3d_passes: memset failed");
         return -2;
     }
@@ -225,13 +223,13 @@ extern "C" int ullsam_split3d_relabel(const unsigned long long* list, long parts
     const long n = (long)Z * H * W;
     ULLSAM_CHECK(parts >= 0 && parts <= n && K <= 2147483646L, "split3d_relabel: need 0 <= parts <= Z * H * W and K <= 2^31 - 2");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (K > 0 && hipMemsetAsync(parts_of, 0, (size_t)K * 4, s) != hipSuccess) {
+    if (!mz_zero(parts_of, (size_t)K * 4, s)) {
         ullsam_set_error("split3d_relabel: memset failed");
         return -2;
     }
-    const unsigned blocks = (unsigned)((n + 255) / 256);
+    const unsigned blocks = mz_blocks(n);
     if (parts > 0) {
-        split3_tables_kernel<<<(unsigned)((parts + 255) / 256), 256, 0, s>>>(reinterpret_cast<const mz_u64*>(list), parts, d2, n, H, W, K, newid, parent, peak_r2,
+        split3_tables_kernel<<<mz_blocks(parts), 256, 0, s>>>(reinterpret_cast<const mz_u64*>(list), parts, d2, n, H, W, K, newid, parent, peak_r2,
                                                                              peak_xyz, parts_of, flags);
         ULLSAM_LAUNCH_CHECK();
     }

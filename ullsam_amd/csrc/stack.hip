@@ -16,14 +16,14 @@
 // arrival.  A second kernel turns the slots into the partners' ids.
 // Link.  mutual: (a, b) is linked iff succ[a] = b and pred[b] = a, so every id has at most one predecessor and the representative of g is the
 // head of its chain: a read-only walk over pred / succ, at most Z steps, every step to a smaller id.  all: every candidate is a link and the
-// representatives come from a union-find that hooks the LARGER root under the smaller one (mosaic.hip's loop), then a flatten pass.
+// representatives come from a union-find that hooks the LARGER root under the smaller one (mz_union, label_common.h), then a flatten pass.
 // Stats.  One wave per row: voxels (64-bit), first and last plane and the inclusive XYXY box per representative, one atomicAdd per run, bounds
 // sent only when a relaxed load says they would improve.
 // Compaction.  One workgroup: keep = voxels != 0 and >= min_volume and last - first + 1 >= min_planes, renumbered 1..K by ascending
 // representative; label_of_global[g] = final label of parent[g].
 // Relabel.  volume[p] = label_of_global[g(z, plane_z[p])], 16 bytes per lane where both buffers allow it; indexed in 64 bits.
 // An id outside 0..K_z reads as background and sets flags[0]; no table is indexed with it.
-#include "pair_table.h"   // the relaxed atomics, the runs of equal keys along a row and the pair table (shared with mosaic.hip and measure.hip)
+#include "pair_table.h"   // the runs of equal keys along a row and the pair table; through it label_common.h: the relaxed atomics, the union-find
 #include <limits.h>
 
 struct SkPlane {
@@ -169,25 +169,6 @@ __global__ __launch_bounds__(256) void stack_chain_kernel(const int* __restrict_
     if (bad) mz_store(flags + 0, 1);
     parent[i] = (int)g;
 }
-__device__ __forceinline__ int sk_find(const int* L, int i) {
-    int q = mz_load(L + i);
-    while (q != i) { i = q; q = mz_load(L + i); }
-    return i;
-}
-__device__ __forceinline__ void sk_union(int* L, int a, int b) {
-    const int a0 = a, b0 = b;
-    for (;;) {
-        a = sk_find(L, a);
-        b = sk_find(L, b);
-        if (a == b) break;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = mz_min(L + a, b);                // a was a root when read: link it under the smaller root
-        if (old == a) { a = b; break; }
-        a = old;                                         // somebody linked a first: a ~ old still has to meet b
-    }
-    if (a < a0) mz_min(L + a0, a);                       // shorten the two chains: a parent only moves down
-    if (a < b0) mz_min(L + b0, a);
-}
 __global__ __launch_bounds__(256) void stack_iota_kernel(long n, int* __restrict__ parent) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) parent[i] = (int)i;
@@ -199,11 +180,11 @@ __global__ __launch_bounds__(256) void stack_merge_kernel(const mz_u64* __restri
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= cap) return;
     const SkCand c = sk_cand(keys, counts, i, areas, G, num, den, flags);
-    if (c.ok) sk_union(parent, (int)c.a, (int)c.b);
+    if (c.ok) mz_union(parent, (int)c.a, (int)c.b);
 }
 __global__ __launch_bounds__(256) void stack_flatten_kernel(long n, int* __restrict__ parent) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) mz_store(parent + i, sk_find(parent, (int)i));   // (whatever a concurrent reader finds at i is an ancestor of i)
+    if (i < n) mz_store(parent + i, mz_find(parent, (int)i));   // (whatever a concurrent reader finds at i is an ancestor of i)
 }
 
 // ---- stats ------------------------------------------------------------------------------------------------------------------------------------
@@ -238,12 +219,12 @@ __global__ __launch_bounds__(256) void stack_stats_kernel(const int* __restrict_
         const int xb = x0 + n - 1;
         int* zr = zrange + 2 * v;
         int* bx = boxes + 4 * v;
-        if (mz_load(zr + 0) > z) mz_min(zr + 0, z);
-        if (mz_load(zr + 1) < z) mz_max(zr + 1, z);
-        if (mz_load(bx + 0) > x0) mz_min(bx + 0, x0);
-        if (mz_load(bx + 1) > y) mz_min(bx + 1, y);
-        if (mz_load(bx + 2) < xb) mz_max(bx + 2, xb);
-        if (mz_load(bx + 3) < y) mz_max(bx + 3, y);
+        mz_send_min(zr + 0, z);
+        mz_send_max(zr + 1, z);
+        mz_send_min(bx + 0, x0);
+        mz_send_min(bx + 1, y);
+        mz_send_max(bx + 2, xb);
+        mz_send_max(bx + 3, y);
     };
     MzRun run = {0, 0, 0};
     bool bad = false;
@@ -310,8 +291,6 @@ __global__ __launch_bounds__(256) void stack_compact_kernel(const long* __restri
 }
 
 // ---- relabel --------------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int sk_look(int l, int b0, int k, const int* __restrict__ log) { return (l > 0 && l <= k) ? log[b0 + l] : 0; }
-
 // grid (ceil(H * W / 1024), Z), block 256: four pixels per thread.  vec: both buffers start on a 16-byte boundary and H * W is a multiple of 4.
 __global__ __launch_bounds__(256) void stack_relabel_kernel(const int* __restrict__ planes, int Z, long HW, const int* __restrict__ base, long G,
                                                             const int* __restrict__ log, int vec, int* __restrict__ volume) {
@@ -327,17 +306,17 @@ __global__ __launch_bounds__(256) void stack_relabel_kernel(const int* __restric
         if (p < HW) {                                    // (HW is a multiple of 4: p + 3 < HW)
             const int4 v = *reinterpret_cast<const int4*>(src + p);
             int4 o;
-            o.x = sk_look(v.x, pl.b0, k, log);
-            o.y = sk_look(v.y, pl.b0, k, log);
-            o.z = sk_look(v.z, pl.b0, k, log);
-            o.w = sk_look(v.w, pl.b0, k, log);
+            o.x = mz_look(v.x, pl.b0, k, log);
+            o.y = mz_look(v.y, pl.b0, k, log);
+            o.z = mz_look(v.z, pl.b0, k, log);
+            o.w = mz_look(v.w, pl.b0, k, log);
             *reinterpret_cast<int4*>(dst + p) = o;
         }
     } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const long p = p0 + j * 256 + threadIdx.x;
-            if (p < HW) dst[p] = sk_look(src[p], pl.b0, k, log);
+            if (p < HW) dst[p] = mz_look(src[p], pl.b0, k, log);
         }
     }
 }
@@ -350,16 +329,13 @@ __global__ __launch_bounds__(256) void stack_relabel_kernel(const int* __restric
     ULLSAM_CHECK(G >= 0 && G <= 2147483646L && cap >= 0 && cap <= (1L << 31), what ": need 0 <= G <= 2^31 - 2 and 0 <= slots <= 2^31"); \
     ULLSAM_CHECK(num > 0 && num <= den && den < (1L << 31), what ": need 0 < num <= den < 2^31")
 
-static bool sk_zero(void* p, size_t bytes, hipStream_t s) { return bytes == 0 || hipMemsetAsync(p, 0, bytes, s) == hipSuccess; }
-static unsigned sk_blocks(long n) { return (unsigned)((n + 255) / 256); }
-
 extern "C" int ullsam_stack_pairs(const int* planes, int Z, int H, int W, const int* base, long G, unsigned long long* keys, int* counts, long cap,
                                   int max_pairs, int* areas, int* flags, void* stream) {
     SK_STACK_CHECK("stack_pairs");
     ULLSAM_CHECK(cap >= 2 && (cap & (cap - 1)) == 0 && max_pairs >= 1 && 2L * max_pairs <= cap && cap <= (1L << 31),
                  "stack_pairs: the capacity must be a power of two with 2 * max_pairs <= capacity <= 2^31");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (!sk_zero(keys, (size_t)cap * 8, s) || !sk_zero(counts, (size_t)cap * 4, s) || !sk_zero(areas, (size_t)(G + 1) * 4, s) || !sk_zero(flags, 16, s)) {
+    if (!mz_zero(keys, (size_t)cap * 8, s) || !mz_zero(counts, (size_t)cap * 4, s) || !mz_zero(areas, (size_t)(G + 1) * 4, s) || !mz_zero(flags, 16, s)) {
         ullsam_set_error("stack_pairs: memset failed");
         return -2;
     }
@@ -373,13 +349,13 @@ extern "C" int ullsam_stack_best(const unsigned long long* keys, const int* coun
                                  int* pred, int* flags, void* stream) {
     SK_TABLE_CHECK("stack_best");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    stack_fill_kernel<<<sk_blocks(G + 1), 256, 0, s>>>(G + 1, succ, pred, -1);
+    stack_fill_kernel<<<mz_blocks(G + 1), 256, 0, s>>>(G + 1, succ, pred, -1);
     ULLSAM_LAUNCH_CHECK();
     if (cap > 0 && G > 0) {
-        stack_best_kernel<<<sk_blocks(cap), 256, 0, s>>>(keys, counts, cap, areas, G, num, den, succ, pred, flags);
+        stack_best_kernel<<<mz_blocks(cap), 256, 0, s>>>(keys, counts, cap, areas, G, num, den, succ, pred, flags);
         ULLSAM_LAUNCH_CHECK();
     }
-    stack_partner_kernel<<<sk_blocks(G + 1), 256, 0, s>>>(keys, cap, G + 1, succ, pred);
+    stack_partner_kernel<<<mz_blocks(G + 1), 256, 0, s>>>(keys, cap, G + 1, succ, pred);
     ULLSAM_LAUNCH_CHECK();
     return 0;
 }
@@ -390,16 +366,16 @@ extern "C" int ullsam_stack_link(const int* succ, const int* pred, const unsigne
     ULLSAM_CHECK((succ != nullptr) == (pred != nullptr), "stack_link: succ and pred come together (mutual) or not at all (every candidate links)");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (succ) {
-        stack_chain_kernel<<<sk_blocks(G + 1), 256, 0, s>>>(succ, pred, G, parent, flags);
+        stack_chain_kernel<<<mz_blocks(G + 1), 256, 0, s>>>(succ, pred, G, parent, flags);
         ULLSAM_LAUNCH_CHECK();
         return 0;
     }
-    stack_iota_kernel<<<sk_blocks(G + 1), 256, 0, s>>>(G + 1, parent);
+    stack_iota_kernel<<<mz_blocks(G + 1), 256, 0, s>>>(G + 1, parent);
     ULLSAM_LAUNCH_CHECK();
     if (cap > 0 && G > 0) {
-        stack_merge_kernel<<<sk_blocks(cap), 256, 0, s>>>(keys, counts, cap, areas, G, num, den, parent, flags);
+        stack_merge_kernel<<<mz_blocks(cap), 256, 0, s>>>(keys, counts, cap, areas, G, num, den, parent, flags);
         ULLSAM_LAUNCH_CHECK();
-        stack_flatten_kernel<<<sk_blocks(G + 1), 256, 0, s>>>(G + 1, parent);
+        stack_flatten_kernel<<<mz_blocks(G + 1), 256, 0, s>>>(G + 1, parent);
         ULLSAM_LAUNCH_CHECK();
     }
     return 0;
@@ -409,7 +385,7 @@ extern "C" int ullsam_stack_stats(const int* planes, int Z, int H, int W, const 
                                   int* boxes_raw, int* flags, void* stream) {
     SK_STACK_CHECK("stack_stats");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    stack_stats_init_kernel<<<sk_blocks(G + 1), 256, 0, s>>>(G + 1, voxels_raw, zrange_raw, boxes_raw);
+    stack_stats_init_kernel<<<mz_blocks(G + 1), 256, 0, s>>>(G + 1, voxels_raw, zrange_raw, boxes_raw);
     ULLSAM_LAUNCH_CHECK();
     stack_stats_kernel<<<dim3((unsigned)((H + 3) / 4), (unsigned)Z), 256, 0, s>>>(planes, Z, H, W, base, G, parent, voxels_raw, zrange_raw, boxes_raw, flags);
     ULLSAM_LAUNCH_CHECK();

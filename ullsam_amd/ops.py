@@ -905,6 +905,33 @@ def _out_i32(out: Optional[torch.Tensor], shape, device, name: str) -> torch.Ten
     return out
 
 
+def _flags_i32(flags: Optional[torch.Tensor], n: int, dev) -> torch.Tensor:
+    """The caller's flags int32 [n], or n zeros."""
+    return torch.zeros((n,), dtype=torch.int32, device=dev) if flags is None else _out_i32(flags, (n,), dev, "flags")
+
+
+def _scan_sums(n: int, chunk: int, dev) -> torch.Tensor:
+    """The per-workgroup sums of a device-wide scan over n values, `chunk` to a workgroup."""
+    return torch.empty((max(1, -(-n // chunk)),), dtype=torch.int32, device=dev)
+
+
+def _num_ids(num, what: str) -> int:
+    k = DISTANCE_INF if num is None else int(num)
+    if not 0 <= k <= DISTANCE_INF:
+        raise _lib.UllsamError(f"{what}: num = {num} must lie in 0..2^31 - 1")
+    return k
+
+
+def _volume_zhw(volume: torch.Tensor, what: str):
+    _chk(volume, "volume", torch.int32)
+    if volume.dim() != 3:
+        raise ValueError(f"{what}: volume must be [Z, H, W], got {tuple(volume.shape)}")
+    z, h, w = volume.shape
+    if not all(1 <= n <= MEASURE3D_MAX_SIDE for n in (z, h, w)) or z * h * w > MEASURE3D_MAX_VOXELS:
+        raise _lib.UllsamError(f"{what}: a volume of {z} x {h} x {w} (each side in 1..{MEASURE3D_MAX_SIDE}, at most 2^31 - 1 voxels)")
+    return z, h, w
+
+
 def rle_paint_labels(counts: torch.Tensor, offsets: torch.Tensor, rank: torch.Tensor, h: int, w: int, out: Optional[torch.Tensor] = None,
                      status: Optional[torch.Tensor] = None):
     """Uncompressed column-major RLEs of one [h, w] frame (counts int32 concatenated, offsets int64 [N + 1]) and their paint ranks (int32 [N],
@@ -1109,10 +1136,6 @@ def _stack_iou(iou, what: str):
     return num, den
 
 
-def _stack_flags(flags: Optional[torch.Tensor], dev) -> torch.Tensor:
-    return torch.zeros((STACK_FLAGS,), dtype=torch.int32, device=dev) if flags is None else _out_i32(flags, (STACK_FLAGS,), dev, "flags")
-
-
 def stack_pairs(planes: torch.Tensor, base: torch.Tensor, g: int, max_pairs: int, flags: Optional[torch.Tensor] = None):
     """planes int32 [Z, H, W], base int32 [Z + 1] (exclusive sum of the planes' id counts, g = base[Z]) -> (keys int64 [slots] -- g_a << 32 | g_b,
     a in plane z and b in plane z + 1, 0 = empty --, counts int32 [slots], areas int32 [g + 1], flags int32 [4]); the caller reads flags."""
@@ -1141,7 +1164,7 @@ def stack_best(keys: torch.Tensor, counts: torch.Tensor, areas: torch.Tensor, g:
     num, den = _stack_iou(iou, "stack_best")
     succ = torch.empty((g + 1,), dtype=torch.int32, device=keys.device)
     pred = torch.empty((g + 1,), dtype=torch.int32, device=keys.device)
-    flags = _stack_flags(flags, keys.device)
+    flags = _flags_i32(flags, STACK_FLAGS, keys.device)
     _lib.call("ullsam_stack_best", keys.data_ptr(), counts.data_ptr(), keys.numel(), areas.data_ptr(), int(g), num, den, succ.data_ptr(), pred.data_ptr(),
               flags.data_ptr(), _stream())
     return succ, pred, flags
@@ -1161,7 +1184,7 @@ def stack_link(g: int, succ: Optional[torch.Tensor] = None, pred: Optional[torch
         _stack_table(keys, counts, areas, g)
         dev, n = keys.device, keys.numel()
     parent = torch.empty((g + 1,), dtype=torch.int32, device=dev)
-    flags = _stack_flags(flags, dev)
+    flags = _flags_i32(flags, STACK_FLAGS, dev)
     _lib.call("ullsam_stack_link", _p(succ), _p(pred), _p(keys), _p(counts), n, _p(areas), int(g), num, den, parent.data_ptr(), flags.data_ptr(), _stream())
     return parent, flags
 
@@ -1176,7 +1199,7 @@ def stack_stats(planes: torch.Tensor, base: torch.Tensor, g: int, parent: torch.
     voxels = torch.empty((g + 1,), dtype=torch.int64, device=dev)
     zrange = torch.empty((g + 1, 2), dtype=torch.int32, device=dev)
     boxes = torch.empty((g + 1, 4), dtype=torch.int32, device=dev)
-    flags = _stack_flags(flags, dev)
+    flags = _flags_i32(flags, STACK_FLAGS, dev)
     _lib.call("ullsam_stack_stats", planes.data_ptr(), z, h, w, base.data_ptr(), int(g), parent.data_ptr(), voxels.data_ptr(), zrange.data_ptr(),
               boxes.data_ptr(), flags.data_ptr(), _stream())
     return voxels, zrange, boxes, flags
@@ -1227,14 +1250,7 @@ def _distance_frame(labels: torch.Tensor, num, what: str):
     h, w = labels.shape
     if not (1 <= h <= DISTANCE_MAX_SIDE and 1 <= w <= DISTANCE_MAX_SIDE):
         raise _lib.UllsamError(f"{what}: a frame of {h} x {w} (each side must lie in 1..{DISTANCE_MAX_SIDE})")
-    k = DISTANCE_INF if num is None else int(num)
-    if not 0 <= k <= DISTANCE_INF:
-        raise _lib.UllsamError(f"{what}: num = {num} must lie in 0..2^31 - 1")
-    return h, w, k
-
-
-def _distance_flags(flags: Optional[torch.Tensor], dev) -> torch.Tensor:
-    return torch.zeros((DISTANCE_FLAGS,), dtype=torch.int32, device=dev) if flags is None else _out_i32(flags, (DISTANCE_FLAGS,), dev, "flags")
+    return h, w, _num_ids(num, what)
 
 
 def distance_columns(labels: torch.Tensor, feature: bool = False, edge: bool = False, num: Optional[int] = None, flags: Optional[torch.Tensor] = None):
@@ -1245,7 +1261,7 @@ def distance_columns(labels: torch.Tensor, feature: bool = False, edge: bool = F
     dev = labels.device
     g = torch.empty((h, w), dtype=torch.uint16, device=dev)
     nearest = torch.empty((h, w), dtype=torch.int32, device=dev) if feature else None
-    flags = _distance_flags(flags, dev)
+    flags = _flags_i32(flags, DISTANCE_FLAGS, dev)
     _lib.call("ullsam_distance_columns", labels.data_ptr(), h, w, int(bool(feature)), int(bool(edge)), k, g.data_ptr(), _p(nearest), flags.data_ptr(), _stream())
     return g, nearest, flags
 
@@ -1268,7 +1284,7 @@ def distance_rows(labels: torch.Tensor, g: torch.Tensor, nearest: Optional[torch
     lim = DISTANCE_INF if limit is None else int(limit)
     if not 0 <= lim <= DISTANCE_INF:
         raise _lib.UllsamError(f"distance_rows: limit = {limit} must lie in 0..2^31 - 1")
-    flags = _distance_flags(flags, dev)
+    flags = _flags_i32(flags, DISTANCE_FLAGS, dev)
     out0 = out1 = best = None
     if mode == "depth":
         if num is None or k > MOSAIC_MAX_IDS:
@@ -1306,10 +1322,7 @@ def _distance3d_volume(volume: torch.Tensor, num, what: str):
     z, h, w = volume.shape
     if not all(1 <= n <= DISTANCE_MAX_SIDE for n in (z, h, w)) or z * h * w > DISTANCE3D_MAX_VOXELS:
         raise _lib.UllsamError(f"{what}: a volume of {z} x {h} x {w} (each side in 1..{DISTANCE_MAX_SIDE}, at most 2^31 - 1 voxels)")
-    k = DISTANCE_INF if num is None else int(num)
-    if not 0 <= k <= DISTANCE_INF:
-        raise _lib.UllsamError(f"{what}: num = {num} must lie in 0..2^31 - 1")
-    return z, h, w, k
+    return z, h, w, _num_ids(num, what)
 
 
 def _distance3d_metric(shape, spacing, edge, what: str):
@@ -1338,7 +1351,7 @@ def distance3d_z(volume: torch.Tensor, feature: bool = False, edge: bool = False
     dev = volume.device
     g = torch.empty((z, h, w), dtype=torch.uint16, device=dev)
     nearest = torch.empty((z, h, w), dtype=torch.int32, device=dev) if feature else None
-    flags = _distance_flags(flags, dev)
+    flags = _flags_i32(flags, DISTANCE_FLAGS, dev)
     _lib.call("ullsam_distance3d_z", volume.data_ptr(), z, h, w, int(bool(feature)), int(bool(edge)), k, g.data_ptr(), _p(nearest), flags.data_ptr(), _stream())
     return g, nearest, flags
 
@@ -1380,7 +1393,7 @@ def distance3d_x(volume: torch.Tensor, h: torch.Tensor, hlabel: Optional[torch.T
     if feat:
         _chk(hlabel, "hlabel", torch.int32)
         assert tuple(hlabel.shape) == (z, hh, w), tuple(hlabel.shape)
-    flags = _distance_flags(flags, dev)
+    flags = _flags_i32(flags, DISTANCE_FLAGS, dev)
     out0 = out1 = best = None
     if mode == "depth":
         if num is None or k > MOSAIC_MAX_IDS:
@@ -1413,10 +1426,6 @@ SPLIT_MAX_DEPTH = 32767
 SPLIT_ROUTES = {"auto": 0, "lds": 1, "global": 2}
 
 
-def _split_flags(flags: Optional[torch.Tensor], dev) -> torch.Tensor:
-    return torch.zeros((SPLIT_FLAGS,), dtype=torch.int32, device=dev) if flags is None else _out_i32(flags, (SPLIT_FLAGS,), dev, "flags")
-
-
 def _split_map(t: torch.Tensor, name: str, like: torch.Tensor, dtype=torch.int32):
     _chk(t, name, dtype)
     assert t.numel() == like.numel(), (name, tuple(t.shape), tuple(like.shape))
@@ -1428,7 +1437,7 @@ def split_ascent(labels: torch.Tensor, d2: torch.Tensor, num: Optional[int] = No
     "lds" / "global": where the 3 x 3 neighbourhood is read from; the output does not depend on it."""
     h, w, k = _distance_frame(labels, num, "split_ascent")
     _split_map(d2, "d2", labels)
-    flags = _split_flags(flags, labels.device)
+    flags = _flags_i32(flags, SPLIT_FLAGS, labels.device)
     up = torch.empty((h, w), dtype=torch.int32, device=labels.device)
     _lib.call("ullsam_split_ascent", labels.data_ptr(), d2.data_ptr(), h, w, k, SPLIT_ROUTES[route], up.data_ptr(), flags.data_ptr(), _stream())
     return up, flags
@@ -1438,7 +1447,7 @@ def split_flatten(up: torch.Tensor, steps: Optional[int] = None, flags: Optional
     """up int32, n pointers -> (up, flags): every pointer replaced, in place, by the root of its chain, after at most `steps` hops (default n)."""
     _chk(up, "up", torch.int32)
     n = up.numel()
-    flags = _split_flags(flags, up.device)
+    flags = _flags_i32(flags, SPLIT_FLAGS, up.device)
     _lib.call("ullsam_split_flatten", up.data_ptr(), n, n if steps is None else int(steps), flags.data_ptr(), _stream())
     return up, flags
 
@@ -1455,7 +1464,7 @@ def split_passes(labels: torch.Tensor, d2: torch.Tensor, up: torch.Tensor, max_p
     cap = mosaic_table_slots(max_pairs)
     keys = torch.empty((cap,), dtype=torch.int64, device=dev)
     vals = torch.empty((cap,), dtype=torch.int32, device=dev)
-    flags = _split_flags(flags, dev)
+    flags = _flags_i32(flags, SPLIT_FLAGS, dev)
     _lib.call("ullsam_split_passes", labels.data_ptr(), d2.data_ptr(), up.data_ptr(), h, w, k, keys.data_ptr(), vals.data_ptr(), cap, max_pairs,
               flags.data_ptr(), _stream())
     return keys, vals, flags
@@ -1474,7 +1483,7 @@ def split_round(keys: torch.Tensor, vals: torch.Tensor, labels: torch.Tensor, d2
     h = int(min_depth)
     if not (0 <= h <= SPLIT_MAX_DEPTH and 0 <= k <= DISTANCE_INF):
         raise _lib.UllsamError(f"split_round: min_depth = {min_depth} must lie in 0..{SPLIT_MAX_DEPTH} and num in 0..2^31 - 1")
-    flags = _split_flags(flags, labels.device)
+    flags = _flags_i32(flags, SPLIT_FLAGS, labels.device)
     _lib.call("ullsam_split_round", keys.data_ptr(), vals.data_ptr(), keys.numel(), labels.data_ptr(), d2.data_ptr(), labels.numel(), k, h, best.data_ptr(),
               up.data_ptr(), changed.data_ptr(), flags.data_ptr(), _stream())
     return flags
@@ -1485,7 +1494,7 @@ def split_collect(labels: torch.Tensor, up: torch.Tensor, parts: Optional[int] =
     label << 32 | p of every representative, in no particular order -- sorting it gives the order of the parts --, flags)."""
     _chk(labels, "labels", torch.int32); _split_map(up, "up", labels)
     k = DISTANCE_INF if num is None else int(num)
-    flags = _split_flags(flags, labels.device)
+    flags = _flags_i32(flags, SPLIT_FLAGS, labels.device)
     lst = None if parts is None else torch.zeros((int(parts),), dtype=torch.int64, device=labels.device)
     _lib.call("ullsam_split_collect", labels.data_ptr(), up.data_ptr(), labels.numel(), k, _p(lst) if lst is not None and lst.numel() else None,
               0 if lst is None else lst.numel(), flags.data_ptr(), _stream())
@@ -1507,7 +1516,7 @@ def split_relabel(parts_sorted: torch.Tensor, labels: torch.Tensor, d2: torch.Te
     peak_r2 = torch.empty((n,), dtype=torch.int32, device=dev)
     peak_xy = torch.empty((n, 2), dtype=torch.int32, device=dev)
     parts_of = torch.empty((k,), dtype=torch.int32, device=dev)
-    flags = _split_flags(flags, dev)
+    flags = _flags_i32(flags, SPLIT_FLAGS, dev)
     _lib.call("ullsam_split_relabel", _p(parts_sorted) if n else None, n, labels.data_ptr(), d2.data_ptr(), up.data_ptr(), h, w, k, newid.data_ptr(),
               out.data_ptr(), parent.data_ptr(), peak_r2.data_ptr(), peak_xy.data_ptr(), _p(parts_of) if k else None, flags.data_ptr(), _stream())
     return out, parent, peak_r2, peak_xy, parts_of, flags
@@ -1530,7 +1539,7 @@ def split3d_ascent(volume: torch.Tensor, d2: torch.Tensor, num: Optional[int] = 
     / "lds" / "global": where the 3 x 3 x 3 neighbourhood is read from; the output does not depend on it."""
     z, h, w, k = _split3d_volume(volume, num, "split3d_ascent")
     _split_map(d2, "d2", volume)
-    flags = _split_flags(flags, volume.device)
+    flags = _flags_i32(flags, SPLIT_FLAGS, volume.device)
     up = torch.empty((z, h, w), dtype=torch.int32, device=volume.device)
     _lib.call("ullsam_split3d_ascent", volume.data_ptr(), d2.data_ptr(), z, h, w, k, SPLIT_ROUTES[route], up.data_ptr(), flags.data_ptr(), _stream())
     return up, flags
@@ -1548,7 +1557,7 @@ def split3d_passes(volume: torch.Tensor, d2: torch.Tensor, up: torch.Tensor, max
     cap = mosaic_table_slots(max_pairs)
     keys = torch.empty((cap,), dtype=torch.int64, device=dev)
     vals = torch.empty((cap,), dtype=torch.int32, device=dev)
-    flags = _split_flags(flags, dev)
+    flags = _flags_i32(flags, SPLIT_FLAGS, dev)
     _lib.call("ullsam_split3d_passes", volume.data_ptr(), d2.data_ptr(), up.data_ptr(), z, h, w, k, keys.data_ptr(), vals.data_ptr(), cap, max_pairs,
               flags.data_ptr(), _stream())
     return keys, vals, flags
@@ -1569,7 +1578,7 @@ def split3d_relabel(parts_sorted: torch.Tensor, volume: torch.Tensor, d2: torch.
     peak_r2 = torch.empty((n,), dtype=torch.int32, device=dev)
     peak_xyz = torch.empty((n, 3), dtype=torch.int32, device=dev)
     parts_of = torch.empty((k,), dtype=torch.int32, device=dev)
-    flags = _split_flags(flags, dev)
+    flags = _flags_i32(flags, SPLIT_FLAGS, dev)
     _lib.call("ullsam_split3d_relabel", _p(parts_sorted) if n else None, n, volume.data_ptr(), d2.data_ptr(), up.data_ptr(), z, h, w, k, newid.data_ptr(),
               out.data_ptr(), parent.data_ptr(), peak_r2.data_ptr(), peak_xyz.data_ptr(), _p(parts_of) if k else None, flags.data_ptr(), _stream())
     return out, parent, peak_r2, peak_xyz, parts_of, flags
@@ -1579,10 +1588,6 @@ def split3d_relabel(parts_sorted: torch.Tensor, volume: torch.Tensor, d2: torch.
 OUTLINE_FLAGS = 8          # bad id / index, E, corners, leaders, list cursor, parent chain too long, (two free)
 OUTLINE_MAX_PIXELS = 2 ** 29
 OUTLINE_CHUNK = 2048       # values per workgroup of the scan (outline.hip OL_CHUNK)
-
-
-def _outline_flags(flags: Optional[torch.Tensor], dev) -> torch.Tensor:
-    return torch.zeros((OUTLINE_FLAGS,), dtype=torch.int32, device=dev) if flags is None else _out_i32(flags, (OUTLINE_FLAGS,), dev, "flags")
 
 
 def _outline_frame(labels: torch.Tensor, what: str):
@@ -1599,22 +1604,16 @@ def _outline_vec(t: torch.Tensor, name: str, n: int, dtype=torch.int32):
     assert t.numel() == n, (name, tuple(t.shape), n)
 
 
-def _outline_sums(n: int, dev) -> torch.Tensor:
-    return torch.empty((max(1, -(-n // OUTLINE_CHUNK)),), dtype=torch.int32, device=dev)
-
-
 def outline_sides(labels: torch.Tensor, num: Optional[int] = None, flags: Optional[torch.Tensor] = None):
     """labels int32 [H, W] -> (mask uint8 [H, W], off int32 [H * W], flags int32 [8]): bit s of mask = side s (top, right, bottom, left) of a labelled
     pixel faces a pixel that is not of its label; off = the exclusive scan of popcount(mask); flags[1] = E, the edges (ullsam_hip.h outline_sides)."""
     h, w = _outline_frame(labels, "outline_sides")
-    k = DISTANCE_INF if num is None else int(num)
-    if not 0 <= k <= DISTANCE_INF:
-        raise _lib.UllsamError(f"outline_sides: num = {num} must lie in 0..2^31 - 1")
+    k = _num_ids(num, "outline_sides")
     dev = labels.device
     mask = torch.empty((h, w), dtype=torch.uint8, device=dev)
     off = torch.empty((h * w,), dtype=torch.int32, device=dev)
-    flags = _outline_flags(flags, dev)
-    _lib.call("ullsam_outline_sides", labels.data_ptr(), h, w, k, mask.data_ptr(), off.data_ptr(), _outline_sums(h * w, dev).data_ptr(), flags.data_ptr(),
+    flags = _flags_i32(flags, OUTLINE_FLAGS, dev)
+    _lib.call("ullsam_outline_sides", labels.data_ptr(), h, w, k, mask.data_ptr(), off.data_ptr(), _scan_sums(h * w, OUTLINE_CHUNK, dev).data_ptr(), flags.data_ptr(),
               _stream())
     return mask, off, flags
 
@@ -1625,7 +1624,7 @@ def outline_scan(vals: torch.Tensor):
     n, dev = vals.numel(), vals.device
     off = torch.empty((n,), dtype=torch.int32, device=dev)
     total = torch.empty((1,), dtype=torch.int32, device=dev)
-    _lib.call("ullsam_outline_scan", _p(vals) if n else None, n, _p(off) if n else None, _outline_sums(n, dev).data_ptr(), total.data_ptr(), _stream())
+    _lib.call("ullsam_outline_scan", _p(vals) if n else None, n, _p(off) if n else None, _scan_sums(n, OUTLINE_CHUNK, dev).data_ptr(), total.data_ptr(), _stream())
     return off, total
 
 
@@ -1641,7 +1640,7 @@ def outline_successors(labels: torch.Tensor, mask: torch.Tensor, off: torch.Tens
     eid = torch.empty((e,), dtype=torch.int32, device=dev)
     succ = torch.empty((e,), dtype=torch.int32, device=dev)
     pdir = torch.empty((e,), dtype=torch.uint8, device=dev)
-    flags = _outline_flags(flags, dev)
+    flags = _flags_i32(flags, OUTLINE_FLAGS, dev)
     _lib.call("ullsam_outline_successors", labels.data_ptr(), h, w, mask.data_ptr(), off.data_ptr(), e, int(connectivity), _p(eid) if e else None,
               _p(succ) if e else None, _p(pdir) if e else None, flags.data_ptr(), _stream())
     return eid, succ, pdir, flags
@@ -1658,7 +1657,7 @@ def outline_rank(succ: torch.Tensor, eid: torch.Tensor, pdir: torch.Tensor, flag
     ws = torch.empty((2, e, 4), dtype=torch.int32, device=dev)
     leader = torch.empty((e,), dtype=torch.int32, device=dev)
     rank = torch.empty((e,), dtype=torch.int32, device=dev)
-    flags = _outline_flags(flags, dev)
+    flags = _flags_i32(flags, OUTLINE_FLAGS, dev)
     _lib.call("ullsam_outline_rank", _p(succ) if e else None, _p(eid) if e else None, _p(pdir) if e else None, e, rounds, _p(ws) if e else None,
               _p(leader) if e else None, _p(rank) if e else None, flags.data_ptr(), _stream())
     return leader, rank, flags
@@ -1671,7 +1670,7 @@ def outline_collect(labels: torch.Tensor, eid: torch.Tensor, leader: torch.Tenso
     e = eid.numel()
     _outline_vec(leader, "leader", e)
     lst = torch.zeros((int(room),), dtype=torch.int64, device=labels.device)
-    flags = _outline_flags(flags, labels.device)
+    flags = _flags_i32(flags, OUTLINE_FLAGS, labels.device)
     _lib.call("ullsam_outline_collect", labels.data_ptr(), labels.numel(), _p(eid) if e else None, _p(leader) if e else None, e,
               _p(lst) if lst.numel() else None, lst.numel(), flags.data_ptr(), _stream())
     return lst, flags
@@ -1685,7 +1684,7 @@ def outline_loops(eid: torch.Tensor, leader: torch.Tensor, loop_of: torch.Tensor
     _outline_vec(leader, "leader", e); _outline_vec(loop_of, "loop_of", e)
     edges = torch.zeros((n,), dtype=torch.int32, device=dev)
     area2 = torch.zeros((n,), dtype=torch.int64, device=dev)
-    flags = _outline_flags(flags, dev)
+    flags = _flags_i32(flags, OUTLINE_FLAGS, dev)
     if e and n:
         _lib.call("ullsam_outline_loops", eid.data_ptr(), leader.data_ptr(), loop_of.data_ptr(), e, n, int(width), edges.data_ptr(), area2.data_ptr(),
                   flags.data_ptr(), _stream())
@@ -1701,7 +1700,7 @@ def outline_order(eid: torch.Tensor, pdir: torch.Tensor, leader: torch.Tensor, r
     _outline_vec(pdir, "pdir", e, torch.uint8); _outline_vec(leader, "leader", e); _outline_vec(rank, "rank", e); _outline_vec(loop_of, "loop_of", e)
     reid = torch.zeros((e,), dtype=torch.int32, device=dev)
     corner = torch.zeros((e,), dtype=torch.uint8, device=dev)
-    flags = _outline_flags(flags, dev)
+    flags = _flags_i32(flags, OUTLINE_FLAGS, dev)
     if e:
         _lib.call("ullsam_outline_order", eid.data_ptr(), pdir.data_ptr(), leader.data_ptr(), rank.data_ptr(), loop_of.data_ptr(), _p(estart) if estart.numel() else None,
                   e, estart.numel(), reid.data_ptr(), corner.data_ptr(), flags.data_ptr(), _stream())
@@ -1729,7 +1728,7 @@ def outline_parents(labels: torch.Tensor, mask: torch.Tensor, off: torch.Tensor,
     e, n, dev = eid.numel(), lead.numel(), labels.device
     _outline_vec(leader, "leader", e); _outline_vec(loop_of, "loop_of", e); _outline_vec(area2, "area2", n, torch.int64)
     parent = torch.empty((n,), dtype=torch.int32, device=dev)
-    flags = _outline_flags(flags, dev)
+    flags = _flags_i32(flags, OUTLINE_FLAGS, dev)
     if n:
         _lib.call("ullsam_outline_parents", labels.data_ptr(), h, w, mask.data_ptr(), off.data_ptr(), eid.data_ptr(), leader.data_ptr(), loop_of.data_ptr(),
                   lead.data_ptr(), area2.data_ptr(), e, n, parent.data_ptr(), flags.data_ptr(), _stream())
@@ -1740,10 +1739,6 @@ def outline_parents(labels: torch.Tensor, mask: torch.Tensor, off: torch.Tensor,
 SIMPLIFY_FLAGS = 4         # an index left its table, (three free)
 SIMPLIFY_MAX_SIDE = 32767
 SIMPLIFY_MAX_T = 255 * 256
-
-
-def _simplify_flags(flags: Optional[torch.Tensor], dev) -> torch.Tensor:
-    return torch.zeros((SIMPLIFY_FLAGS,), dtype=torch.int32, device=dev) if flags is None else _out_i32(flags, (SIMPLIFY_FLAGS,), dev, "flags")
 
 
 def _simplify_frame(h: int, w: int, what: str):
@@ -1762,7 +1757,7 @@ def simplify_flags(labels: torch.Tensor, reid: torch.Tensor, corner: torch.Tenso
     e, dev = reid.numel(), labels.device
     _outline_vec(corner, "corner", e, torch.uint8)
     cand = torch.zeros((e,), dtype=torch.uint8, device=dev)
-    flags = _simplify_flags(flags, dev)
+    flags = _flags_i32(flags, SIMPLIFY_FLAGS, dev)
     if e:
         _lib.call("ullsam_simplify_flags", labels.data_ptr(), h, w, reid.data_ptr(), corner.data_ptr(), e, cand.data_ptr(), flags.data_ptr(), _stream())
     return cand, flags
@@ -1782,7 +1777,7 @@ def simplify_candidates(reid: torch.Tensor, cand: torch.Tensor, coff: torch.Tens
     cloop = torch.full((c,), -1, dtype=torch.int32, device=dev)
     kept = torch.zeros((c,), dtype=torch.uint8, device=dev)
     nfixed = torch.zeros((n,), dtype=torch.int32, device=dev)
-    flags = _simplify_flags(flags, dev)
+    flags = _flags_i32(flags, SIMPLIFY_FLAGS, dev)
     if c and n:
         _lib.call("ullsam_simplify_candidates", reid.data_ptr(), cand.data_ptr(), coff.data_ptr(), estart.data_ptr(), e, n, c, h, w, cxy.data_ptr(),
                   cloop.data_ptr(), kept.data_ptr(), nfixed.data_ptr(), flags.data_ptr(), _stream())
@@ -1802,7 +1797,7 @@ def simplify_anchors(cxy: torch.Tensor, cloop: torch.Tensor, nfixed: torch.Tenso
     """Marks, IN kept, the two anchors of every loop without a fixed point (ullsam_hip.h simplify_anchors) -> (kept, flags)."""
     c, n = _simplify_table(cxy, cloop, kept, nfixed.numel(), "simplify_anchors")
     _chk(nfixed, "nfixed", torch.int32)
-    flags = _simplify_flags(flags, cxy.device)
+    flags = _flags_i32(flags, SIMPLIFY_FLAGS, cxy.device)
     if c and n:
         ws = torch.empty((2, n), dtype=torch.int64, device=cxy.device)
         _lib.call("ullsam_simplify_anchors", cxy.data_ptr(), cloop.data_ptr(), nfixed.data_ptr(), c, n, ws.data_ptr(), kept.data_ptr(), flags.data_ptr(), _stream())
@@ -1819,7 +1814,7 @@ def simplify_segments(kept: torch.Tensor, cloop: torch.Tensor, cstart: torch.Ten
         raise _lib.UllsamError(f"simplify_segments: {n} loops of {c} candidates (need L <= C)")
     pa = torch.full((c,), -1, dtype=torch.int32, device=dev)
     pb = torch.full((c,), -1, dtype=torch.int32, device=dev)
-    flags = _simplify_flags(flags, dev)
+    flags = _flags_i32(flags, SIMPLIFY_FLAGS, dev)
     if c:
         koff, total = outline_scan(kept)
         klist = torch.empty((c,), dtype=torch.int32, device=dev)
@@ -1840,7 +1835,7 @@ def simplify_rounds(cxy: torch.Tensor, cloop: torch.Tensor, cstart: torch.Tensor
         raise _lib.UllsamError(f"simplify_rounds: t = {t} must lie in 0..{SIMPLIFY_MAX_T} and rounds = {rounds} in 1..1024")
     dev = cxy.device
     counts = torch.zeros((rounds,), dtype=torch.int32, device=dev)
-    flags = _simplify_flags(flags, dev)
+    flags = _flags_i32(flags, SIMPLIFY_FLAGS, dev)
     if c:
         ws = torch.empty((3, c), dtype=torch.int64, device=dev)
         _lib.call("ullsam_simplify_rounds", cxy.data_ptr(), cloop.data_ptr(), cstart.data_ptr(), c, n, t * t, rounds, ws.data_ptr(), pa.data_ptr(), pb.data_ptr(),
@@ -1861,7 +1856,7 @@ def simplify_rings(cxy: torch.Tensor, cloop: torch.Tensor, kept: torch.Tensor, v
     vertices = torch.zeros((nv, 2), dtype=torch.int32, device=dev)
     nvert = torch.zeros((n,), dtype=torch.int32, device=dev)
     area2 = torch.zeros((n,), dtype=torch.int64, device=dev)
-    flags = _simplify_flags(flags, dev)
+    flags = _flags_i32(flags, SIMPLIFY_FLAGS, dev)
     if c and n and nv:
         klist = torch.empty((c,), dtype=torch.int32, device=dev)
         _lib.call("ullsam_simplify_rings", cxy.data_ptr(), cloop.data_ptr(), kept.data_ptr(), voff.data_ptr(), total.data_ptr(), cstart.data_ptr(), c, n, nv,
@@ -1877,19 +1872,11 @@ RASTER_CHUNK = 2048        # values per workgroup of the scan (raster.hip RS_CHU
 RASTER_FORMS = {"waves": 0, "pixels": 1}
 
 
-def _raster_flags(flags: Optional[torch.Tensor], dev) -> torch.Tensor:
-    return torch.zeros((RASTER_FLAGS,), dtype=torch.int32, device=dev) if flags is None else _out_i32(flags, (RASTER_FLAGS,), dev, "flags")
-
-
 def _raster_frame(h: int, w: int, num: int, what: str):
     h, w, k = int(h), int(w), int(num)
     if not (1 <= h <= RASTER_MAX_SIDE and 1 <= w <= RASTER_MAX_SIDE and 0 <= k <= RASTER_MAX_IDS):
         raise _lib.UllsamError(f"{what}: a frame of {h} x {w} with {k} ids (each side in 1..32767, at most 65535 ids)")
     return h, w, k
-
-
-def _raster_sums(n: int, dev) -> torch.Tensor:
-    return torch.empty((max(1, -(-n // RASTER_CHUNK)),), dtype=torch.int32, device=dev)
 
 
 def raster_scan(vals: torch.Tensor, flags: Optional[torch.Tensor] = None):
@@ -1899,8 +1886,8 @@ def raster_scan(vals: torch.Tensor, flags: Optional[torch.Tensor] = None):
     n, dev = vals.numel(), vals.device
     off = torch.empty((n,), dtype=torch.int32, device=dev)
     total = torch.empty((1,), dtype=torch.int32, device=dev)
-    flags = _raster_flags(flags, dev)
-    _lib.call("ullsam_raster_scan", _p(vals) if n else None, n, _p(off) if n else None, _raster_sums(n, dev).data_ptr(), total.data_ptr(), flags.data_ptr(),
+    flags = _flags_i32(flags, RASTER_FLAGS, dev)
+    _lib.call("ullsam_raster_scan", _p(vals) if n else None, n, _p(off) if n else None, _scan_sums(n, RASTER_CHUNK, dev).data_ptr(), total.data_ptr(), flags.data_ptr(),
               _stream())
     return off, total, flags
 
@@ -1914,10 +1901,10 @@ def raster_edges(q: torch.Tensor, start: torch.Tensor, ring_label: torch.Tensor,
     n, r, dev = q.shape[0], ring_label.numel(), q.device
     assert start.numel() == r + 1 and (r >= 1 or n == 0), (tuple(start.shape), r, n)
     row0, cnt, nxt, elab, off = (torch.empty((n,), dtype=torch.int32, device=dev) for _ in range(5))
-    flags = _raster_flags(flags, dev)
+    flags = _flags_i32(flags, RASTER_FLAGS, dev)
     if n:
         _lib.call("ullsam_raster_edges", q.data_ptr(), n, start.data_ptr(), r, ring_label.data_ptr(), h, w, k, row0.data_ptr(), cnt.data_ptr(), nxt.data_ptr(),
-                  elab.data_ptr(), off.data_ptr(), _raster_sums(n, dev).data_ptr(), flags.data_ptr(), _stream())
+                  elab.data_ptr(), off.data_ptr(), _scan_sums(n, RASTER_CHUNK, dev).data_ptr(), flags.data_ptr(), _stream())
     return row0, cnt, nxt, elab, off, flags
 
 
@@ -1934,7 +1921,7 @@ def raster_keys(q: torch.Tensor, row0: torch.Tensor, cnt: torch.Tensor, nxt: tor
     if not 0 <= c <= DISTANCE_INF or (c and not n):
         raise _lib.UllsamError(f"raster_keys: crossings = {crossings} must lie in 0..2^31 - 1, and 0 without an edge")
     keys = torch.zeros((c,), dtype=torch.int64, device=dev)
-    flags = _raster_flags(flags, dev)
+    flags = _flags_i32(flags, RASTER_FLAGS, dev)
     if c:
         _lib.call("ullsam_raster_keys", q.data_ptr(), n, row0.data_ptr(), cnt.data_ptr(), nxt.data_ptr(), elab.data_ptr(), off.data_ptr(), c, h, w, k,
                   keys.data_ptr(), flags.data_ptr(), _stream())
@@ -1955,7 +1942,7 @@ def raster_covered(keys: torch.Tensor, h: int, w: int, num: int, flags: Optional
     c, dev = _raster_sorted(keys, "raster_covered"), keys.device
     covered = torch.zeros((k,), dtype=torch.int32, device=dev)
     length = torch.zeros((c // 2,), dtype=torch.int32, device=dev)
-    flags = _raster_flags(flags, dev)
+    flags = _flags_i32(flags, RASTER_FLAGS, dev)
     if c and k:
         _lib.call("ullsam_raster_covered", keys.data_ptr(), c, h, w, k, covered.data_ptr(), length.data_ptr(), flags.data_ptr(), _stream())
     return covered, length, flags
@@ -1971,7 +1958,7 @@ def raster_paint(keys: torch.Tensor, rank: torch.Tensor, h: int, w: int, form: s
     c, dev = _raster_sorted(keys, "raster_paint"), keys.device
     if form not in RASTER_FORMS:
         raise _lib.UllsamError(f'raster_paint: form must be "waves" or "pixels", got {form!r}')
-    flags = _raster_flags(flags, dev)
+    flags = _flags_i32(flags, RASTER_FLAGS, dev)
     if not (c and k):
         return torch.zeros((h, w), dtype=torch.int32, device=dev), flags
     poff = total = None
@@ -1997,7 +1984,7 @@ def raster_finish(raw: torch.Tensor, label_of: torch.Tensor, flags: Optional[tor
     labels = torch.empty((h, w), dtype=torch.int32, device=dev)
     area = torch.empty((k,), dtype=torch.int32, device=dev)
     box = torch.empty((k, 4), dtype=torch.int32, device=dev)
-    flags = _raster_flags(flags, dev)
+    flags = _flags_i32(flags, RASTER_FLAGS, dev)
     _lib.call("ullsam_raster_finish", raw.data_ptr(), h, w, label_of.data_ptr(), k, labels.data_ptr(), _p(area) if k else None, _p(box) if k else None,
               flags.data_ptr(), _stream())
     return labels, area, box, flags
@@ -2093,12 +2080,7 @@ MEASURE3D_LDS_SLOTS = 128             # the default route: the LDS table, 2 - 3 
 
 
 def _measure3d_volume(volume: torch.Tensor, num: int, what: str):
-    _chk(volume, "volume", torch.int32)
-    if volume.dim() != 3:
-        raise ValueError(f"{what}: volume must be [Z, H, W], got {tuple(volume.shape)}")
-    z, h, w = volume.shape
-    if not all(1 <= n <= MEASURE3D_MAX_SIDE for n in (z, h, w)) or z * h * w > MEASURE3D_MAX_VOXELS:
-        raise _lib.UllsamError(f"{what}: a volume of {z} x {h} x {w} (each side in 1..{MEASURE3D_MAX_SIDE}, at most 2^31 - 1 voxels)")
+    z, h, w = _volume_zhw(volume, what)
     if not 0 <= int(num) <= MOSAIC_MAX_IDS:
         raise _lib.UllsamError(f"{what}: num = {num} must lie in 0..2^31 - 2")
     return z, h, w
@@ -2170,12 +2152,7 @@ MESH3D_BLOCK_KEYS = 2048              # sorted keys per workgroup of the heads /
 
 
 def _mesh3d_volume(volume: torch.Tensor, num: int, what: str, max_label: int):
-    _chk(volume, "volume", torch.int32)
-    if volume.dim() != 3:
-        raise ValueError(f"{what}: volume must be [Z, H, W], got {tuple(volume.shape)}")
-    z, h, w = volume.shape
-    if not all(1 <= n <= MEASURE3D_MAX_SIDE for n in (z, h, w)) or z * h * w > MEASURE3D_MAX_VOXELS:
-        raise _lib.UllsamError(f"{what}: a volume of {z} x {h} x {w} (each side in 1..{MEASURE3D_MAX_SIDE}, at most 2^31 - 1 voxels)")
+    z, h, w = _volume_zhw(volume, what)
     if not 0 <= int(num) <= max_label:
         raise _lib.UllsamError(f"{what}: num = {num} must lie in 0..{max_label}")
     return z, h, w
