@@ -766,6 +766,26 @@ int ullsam_mesh3d_quads(const unsigned long long* fkeys, long F, const unsigned 
 int ullsam_mesh3d_starts(const unsigned long long* sorted, long n, int K, long* start, void* stream);
 int ullsam_mesh3d_topology(const int* volume, int Z, int H, int W, int K, long* euler, long* pinch_edges, int* flags, void* stream);
 
+/* Skeletons of a label image: Guo and Hall's two-sub-iteration parallel thinning of every instance at once, and the links, degrees and node
+   classes of the result (csrc/skeleton.hip; integer work, bit-exact with the host form utils.skeleton; definition in DESIGN.md "7b, continued
+   (skeletons)").  An image i32 [H, W], 1 <= H, W <= 32767, holds a pixel's positive label while it stands and 0 on the background and once it is
+   deleted; a neighbour is ON when it lies in the frame and holds the pixel's label; the code of a pixel has bit i for N, NE, E, SE, S, SW, W, NW
+   (y down); sub-iteration `index` deletes the pixels whose code its table (by index & 1) holds, all judged on the state at its start.
+   flags i32 [4], zeroed by the caller, only ever raised: [0] = a label below 0 (skel_measure: outside 0..K); it reads as background; [1] = a
+   pixel was deleted in a sub-iteration whose index is >= limit.
+   skel_step: dst = src after sub-iteration `index`; count[0] += the pixels deleted (one atomic per wave).  src and dst must differ.
+   skel_tile: dst = src after the 8 sub-iterations index .. index + 7, run on tiles of 64 x 32 pixels staged in LDS with a halo of 8;
+     counts[j] += the pixels sub-iteration index + j deleted, j = 0..7.  The outputs equal those of eight skel_step launches.
+   skel_measure: two pixels of one label are linked when 4-adjacent, or diagonal with neither pixel 4-adjacent to both holding the label; the
+     degree of a pixel = its links.  table i64 [7, K] (zeroed by the caller; NULL: none), row f column k - 1 += over id k's pixels: 1, degree
+     == 1, degree >= 3, degree == 0, its links right and down, its links down-right and down-left, its degree.  d2 i32 [H, W] or NULL: d2_sum
+     i64 [K] (zeroed) += d2, d2_min / d2_max i32 [K] (set to 2^31 - 1 / -1 by the caller) take the minimum / maximum.  nodes u8 [H, W] or NULL:
+     0 off, 1 degree 1, 2 degree 2, 3 degree >= 3, 4 degree 0. */
+int ullsam_skel_step(const int* src, int* dst, int H, int W, int index, int limit, int* count, int* flags, void* stream);
+int ullsam_skel_tile(const int* src, int* dst, int H, int W, int index, int limit, int* counts, int* flags, void* stream);
+int ullsam_skel_measure(const int* skeleton, const int* d2, int H, int W, long K, long* table, long* d2_sum, int* d2_min, int* d2_max,
+                        unsigned char* nodes, int* flags, void* stream);
+
 /* Point prompts, boxes and per-instance masks from one instance label image (csrc/prompts.hip; the reference's dataset loop
    train_joint_v2.py:313-468 as integer kernels, bit-exact with utils.prompts' host route; definitions in DESIGN.md "7b, continued (prompts)").
    labels i32 [H, W], 0 = background, ids 1..65535; H * W < 2^31; radius, hi <= 64; num_pos, num_neg <= 16.

@@ -65,6 +65,9 @@ HOT_MEASURE3D = [r"measure3d_kernelILi\dE", r"contacts3d_kernel", r"measure3d_in
 # corner keys, the heads of the sorted corner keys counted and written, quad indices, per-id offsets, init, topology.  A list of its own: it is in no aggregate.
 HOT_MESH3D = [r"mesh3d_mask_kernel", r"mesh3d_scan_kernel", r"mesh3d_faces_kernel", r"mesh3d_corners_kernel", r"mesh3d_heads_kernelILb[01]E",
               r"mesh3d_quads_kernel", r"mesh3d_starts_kernel", r"mesh3d_init_kernel", r"mesh3d_topology_kernel"]
+# skeletons of a label image (csrc/skeleton.hip): one sub-iteration from global memory, eight on a tile in LDS, links / degrees / tables.  A list
+# of its own: it is in no aggregate.
+HOT_SKELETON = [r"skel_step_kernel", r"skel_lds_kernel", r"skel_nodes_kernel"]
 HOT_BF16 = (HOT_BF16 + HOT_AMG + HOT_REGIONS + HOT_DECODE_FP8 + HOT_LABELS + HOT_MEASURE + HOT_DISTANCE + HOT_SPLIT + HOT_OUTLINE + HOT_RASTER
             + HOT_DISTANCE3D + HOT_SPLIT3D + HOT_MEASURE3D)
 HOT = HOT_BF16

@@ -164,6 +164,9 @@ SIGNATURES = {
     "ullsam_mesh3d_quads": [vp, i64, vp, i64, i32, i32, vp, vp],
     "ullsam_mesh3d_starts": [vp, i64, i32, vp, vp],
     "ullsam_mesh3d_topology": [vp, i32, i32, i32, i32, vp, vp, vp, vp],
+    "ullsam_skel_step": [vp, vp, i32, i32, i32, i32, vp, vp, vp],
+    "ullsam_skel_tile": [vp, vp, i32, i32, i32, i32, vp, vp, vp],
+    "ullsam_skel_measure": [vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp],
     "ullsam_label_d1": [vp, i32, i32, i32, vp, vp, vp, vp],
     "ullsam_prompt_choose": [vp, i32, C.c_ulonglong, vp, vp, vp, vp, vp],
     "ullsam_prompt_sets": [vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],

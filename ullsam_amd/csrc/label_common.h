@@ -1,5 +1,5 @@
 // The common layer of the label-image kernels (labels, regions, prompts, mosaic, stack, distance*, split*, measure*, outline, simplify, raster,
-// mesh3d): relaxed agent-scope atomics, the lock-free union-find over a global parent array, the wave and workgroup scans, the per-label LDS slot
+// mesh3d, skeleton): relaxed agent-scope atomics, the lock-free union-find over a global parent array, the wave and workgroup scans, the per-label LDS slot
 // claim of the measurement kernels, and the host one-liners of the C ABI.  Integer work only.  pair_table.h builds the row runs and the pair table
 // on top of this; a new label kernel takes its helpers from these two headers and defines none of them again.
 #pragma once

@@ -1584,6 +1584,76 @@ def split3d_relabel(parts_sorted: torch.Tensor, volume: torch.Tensor, d2: torch.
     return out, parent, peak_r2, peak_xyz, parts_of, flags
 
 
+# ---- skeletons of a label image (csrc/skeleton.hip; utils.skeleton drives these) ---------------------------------------------------------------
+SKEL_FLAGS = 4             # bad id, a deletion at or past the limit, (two free)
+SKEL_TILE_STEPS = 8        # the sub-iterations of one skel_tile launch = the depth of its halo (skeleton.hip SK_S)
+SKEL_TILE = (32, 64)       # its core, rows x columns (skeleton.hip SK_CH, SK_CW)
+SKEL_BLOCK = 32            # the sub-iterations the driver launches between two read-backs of the counters
+SKEL_FIELDS = ("pixels", "end_points", "junctions", "isolated", "links_orth", "links_diag", "degree_sum")
+
+
+def _skel_pair(src: torch.Tensor, dst: Optional[torch.Tensor], index: int, limit: int, counts: Optional[torch.Tensor], n: int, what: str):
+    h, w, _ = _distance_frame(src, None, what)
+    dst = _out_i32(dst, (h, w), src.device, "dst")
+    if dst.data_ptr() == src.data_ptr():
+        raise _lib.UllsamError(f"{what}: src and dst must be two images")
+    index, limit = int(index), int(limit)
+    if not (0 <= index <= DISTANCE_INF - n and 0 <= limit <= DISTANCE_INF):
+        raise _lib.UllsamError(f"{what}: index = {index} and limit = {limit} must lie in 0..2^31 - 1")
+    counts = torch.zeros((n,), dtype=torch.int32, device=src.device) if counts is None else _out_i32(counts, (n,), src.device, "counts")
+    return h, w, dst, index, limit, counts
+
+
+def skel_step(src: torch.Tensor, dst: Optional[torch.Tensor], index: int, limit: int = DISTANCE_INF, counts: Optional[torch.Tensor] = None,
+              flags: Optional[torch.Tensor] = None):
+    """src int32 [H, W] -> (dst int32 [H, W], counts int32 [1], flags int32 [4]): one sub-iteration of the thinning (ullsam_hip.h skel_step), number
+    `index` (its parity picks the table); counts[0] += the pixels it deleted; flags[1] is raised when it deleted one and index >= limit."""
+    h, w, dst, index, limit, counts = _skel_pair(src, dst, index, limit, counts, 1, "skel_step")
+    flags = _flags_i32(flags, SKEL_FLAGS, src.device)
+    _lib.call("ullsam_skel_step", src.data_ptr(), dst.data_ptr(), h, w, index, limit, counts.data_ptr(), flags.data_ptr(), _stream())
+    return dst, counts, flags
+
+
+def skel_tile(src: torch.Tensor, dst: Optional[torch.Tensor], index: int, limit: int = DISTANCE_INF, counts: Optional[torch.Tensor] = None,
+              flags: Optional[torch.Tensor] = None):
+    """src int32 [H, W] -> (dst int32 [H, W], counts int32 [SKEL_TILE_STEPS], flags int32 [4]): the sub-iterations index .. index +
+    SKEL_TILE_STEPS - 1 in one launch on tiles staged in LDS (ullsam_hip.h skel_tile); counts[j] += the pixels sub-iteration index + j deleted."""
+    h, w, dst, index, limit, counts = _skel_pair(src, dst, index, limit, counts, SKEL_TILE_STEPS, "skel_tile")
+    flags = _flags_i32(flags, SKEL_FLAGS, src.device)
+    _lib.call("ullsam_skel_tile", src.data_ptr(), dst.data_ptr(), h, w, index, limit, counts.data_ptr(), flags.data_ptr(), _stream())
+    return dst, counts, flags
+
+
+def skel_measure(skeleton: torch.Tensor, num: Optional[int], d2: Optional[torch.Tensor] = None, nodes: bool = False, flags: Optional[torch.Tensor] = None):
+    """skeleton int32 [H, W] -> (table or None, nodes uint8 [H, W] or None, flags int32 [4]) (ullsam_hip.h skel_measure).  num = K: the table is a
+    dict of int64 [K] per SKEL_FIELDS, with d2 (int32 [H, W]) also d2_sum int64 [K], d2_min / d2_max int32 [K]; num None: no table, every positive
+    id is live.  nodes: the node classes as well."""
+    h, w, k = _distance_frame(skeleton, num, "skel_measure")
+    dev = skeleton.device
+    flags = _flags_i32(flags, SKEL_FLAGS, dev)
+    table = d2_sum = d2_min = d2_max = None
+    if num is not None:
+        if k > DISTANCE_INF - 1:
+            raise _lib.UllsamError("skel_measure: num must lie in 0..2^31 - 2")
+        table = torch.zeros((len(SKEL_FIELDS), k), dtype=torch.int64, device=dev)
+        if d2 is not None:
+            _split_map(d2, "d2", skeleton)
+            d2_sum = torch.zeros((k,), dtype=torch.int64, device=dev)
+            d2_min = torch.full((k,), DISTANCE_INF, dtype=torch.int32, device=dev)
+            d2_max = torch.full((k,), -1, dtype=torch.int32, device=dev)
+    out = torch.empty((h, w), dtype=torch.uint8, device=dev) if nodes else None
+    with_d2 = d2_sum is not None
+    some = with_d2 and k > 0                              # (an empty tensor has no address)
+    _lib.call("ullsam_skel_measure", skeleton.data_ptr(), _p(d2) if some else None, h, w, k, _p(table) if table is not None and k else None,
+              _p(d2_sum) if some else None, _p(d2_min) if some else None, _p(d2_max) if some else None, _p(out), flags.data_ptr(), _stream())
+    res = None
+    if table is not None:
+        res = {f: table[i] for i, f in enumerate(SKEL_FIELDS)}
+        if with_d2:
+            res.update(d2_sum=d2_sum, d2_min=d2_min, d2_max=d2_max)
+    return res, out, flags
+
+
 # ---- outlines of a label image: polygon loops (csrc/outline.hip; utils.outline drives these) --------------------------------------------------
 OUTLINE_FLAGS = 8          # bad id / index, E, corners, leaders, list cursor, parent chain too long, (two free)
 OUTLINE_MAX_PIXELS = 2 ** 29

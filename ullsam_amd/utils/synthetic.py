@@ -82,6 +82,40 @@ def label_frame(seed: int, height: int, width: int, n_cells: int, r_range: Tuple
     return labels
 
 
+def filament_frame(seed: int, height: int, width: int, n_instances: int, branches: Tuple[int, int] = (2, 4), segments: Tuple[int, int] = (2, 4),
+                   step: Tuple[float, float] = (0.04, 0.12), brush: Tuple[int, int] = (1, 3)) -> np.ndarray:
+    """-> int32 [height, width] label image of branched filaments (neurites, hyphae) for the skeleton bench and tests: instance i carries id i + 1
+    and is a few random polylines from one root -- branches[0]..branches[1] of them, each of segments[0]..segments[1] segments whose lengths are
+    step[0]..step[1] of the frame's longer side, every polyline but the first starting at a vertex of an earlier one -- drawn with a disc brush of
+    radius brush[0]..brush[1] pixels (one radius per instance).  Later instances on top.  Deterministic in `seed`."""
+    rng = np.random.default_rng([int(seed), 0xF11A])
+    size = max(height, width)
+    labels = np.zeros((height, width), np.int32)
+    for i in range(n_instances):
+        r = int(rng.integers(brush[0], brush[1] + 1))
+        vertices = [(rng.uniform(0, width), rng.uniform(0, height))]
+        pts = []
+        for _ in range(int(rng.integers(branches[0], branches[1] + 1))):
+            x, y = vertices[int(rng.integers(0, len(vertices)))]
+            ang = rng.uniform(0, 2 * math.pi)
+            for _ in range(int(rng.integers(segments[0], segments[1] + 1))):
+                ang += rng.uniform(-0.9, 0.9)
+                ln = rng.uniform(step[0], step[1]) * size
+                nx, ny = x + ln * math.cos(ang), y + ln * math.sin(ang)
+                t = np.linspace(0.0, 1.0, int(2 * ln) + 2)
+                pts.append(np.stack([np.rint(y + (ny - y) * t), np.rint(x + (nx - x) * t)], 1).astype(np.int64))
+                x, y = nx, ny
+                vertices.append((x, y))
+        centres = np.unique(np.concatenate(pts), axis=0)
+        for dy in range(-r, r + 1):
+            for dx in range(-r, r + 1):
+                if dy * dy + dx * dx <= r * r:
+                    ys, xs = centres[:, 0] + dy, centres[:, 1] + dx
+                    ok = (ys >= 0) & (ys < height) & (xs >= 0) & (xs < width)
+                    labels[ys[ok], xs[ok]] = i + 1
+    return labels
+
+
 def label_stack(seed: int, Z: int, H: int, W: int, n_cells: int, r_range: Tuple[float, float], dz: float):
     """-> (planes int32 [Z, H, W], counts): spheres ("cells" in a z-stack) cut by Z planes dz apart (in pixels), every plane numbering the
     cells IT sees 1..K_z by a permutation of its own, so that the same cell carries unrelated ids in neighbouring planes and linking by
